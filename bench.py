@@ -18,6 +18,10 @@ Usage:
   python bench.py --gpus 8 --steps 64     # under torch.distributed.run
   python bench.py --bench-config bert     # BASELINE config 3
   python bench.py --encoding proto        # python-protobuf client (A/B)
+  python bench.py --dump-outputs DIR      # last timed step's outputs as .npy
+
+Inputs are seeded, so two runs with the same arguments send identical
+requests and their --dump-outputs files can be compared array for array.
 """
 from __future__ import annotations
 
@@ -60,13 +64,14 @@ def _server_proc(address: str, ready, stop, servable: str = "echo",
 
 
 def make_inputs(cfg: str, device, batch_override=None):
+    # seeded CPU generator: identical inputs from run to run on any device
+    g = torch.Generator(device="cpu").manual_seed(0)
     if cfg == "resnet50":
         b = batch_override or 32
-        return {"images": torch.randn(b, 3, 224, 224, device=device,
-                                      dtype=torch.float32)}
+        return {"images": torch.randn(b, 3, 224, 224, generator=g,
+                                      dtype=torch.float32).to(device)}
     if cfg == "bert":
         b = batch_override or 128
-        g = torch.Generator(device="cpu").manual_seed(0)
         ids = torch.randint(0, 30522, (b, 512), generator=g,
                             dtype=torch.int32).to(device)
         mask = torch.ones(b, 512, dtype=torch.int32, device=device)
@@ -75,9 +80,36 @@ def make_inputs(cfg: str, device, batch_override=None):
         return {"x": torch.zeros((), dtype=torch.float32, device=device)}
     if cfg in ("bf16pack", "fused"):
         b = batch_override or 32
-        return {"images": torch.randn(b, 3, 224, 224, device=device,
-                                      dtype=torch.bfloat16)}
+        return {"images": torch.randn(b, 3, 224, 224, generator=g,
+                                      dtype=torch.bfloat16).to(device)}
     raise ValueError(f"unknown bench config {cfg}")
+
+
+_DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(outs, out_dir: str) -> None:
+    """Write each output of one step as out_dir/<name>.npy: float32 for
+    float dtypes up to 32 bits, float64 otherwise (exact for int32). The
+    64 MB budget is split evenly; a larger array is stored as a fixed,
+    seeded sample of its flattened elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    budget = _DUMP_BUDGET_BYTES // max(1, len(outs))
+    for name in sorted(outs):
+        v = outs[name]
+        if isinstance(v, torch.Tensor):
+            wide = (not v.dtype.is_floating_point) or v.element_size() > 4
+            arr = v.detach().to("cpu").to(
+                torch.float64 if wide else torch.float32).numpy()
+        else:
+            arr = np.asarray(v)
+            arr = arr.astype(np.float32 if arr.dtype.kind == "f"
+                             and arr.itemsize <= 4 else np.float64)
+        if arr.nbytes > budget:
+            idx = np.random.default_rng(0).choice(
+                arr.size, budget // arr.itemsize, replace=False)
+            arr = arr.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
 
 
 def main():
@@ -136,6 +168,16 @@ def main():
                          "consecutive requests). Default: 4 single-rank "
                          "over gRPC (measured peak with shards 4), 1 "
                          "multi-rank/shm")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the "
+                         "last timed step to DIR/<name>.npy (float32/"
+                         "float64, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline "
+                         "figure; this benchmark has none (the A/B "
+                         "matrices and per-stage breakdowns are separate "
+                         "programs under tools/), so the flag is accepted "
+                         "and changes nothing")
     args = ap.parse_args()
     if args.shards < 0:
         args.shards = 1 if args.transport == "shm" else 4
@@ -356,13 +398,14 @@ def main():
 
     def run_pipelined(nsteps):
         """Sliding window of `pipeline` in-flight requests; returns
-        per-request submit->complete latencies. With --shards > 1 each
-        in-flight request is itself shard-parallel (thread pool of
-        `pipeline` sharded calls)."""
+        per-request submit->complete latencies and the outputs of the
+        last request. With --shards > 1 each in-flight request is itself
+        shard-parallel (thread pool of `pipeline` sharded calls)."""
         out_dev = f"cuda:{local_rank}" if has_gpu else "cpu"
         lat_local = []
         inflight = []
         submitted = 0
+        last = None
         if args.shards > 1:
             from concurrent.futures import ThreadPoolExecutor
             pool = ThreadPoolExecutor(max_workers=args.pipeline)
@@ -374,16 +417,19 @@ def main():
                 done = 0
                 while done < nsteps:
                     fut, ts = inflight.pop(0)
-                    fut.result()
+                    outs = fut.result()
                     lat_local.append(time.perf_counter() - ts)
                     done += 1
+                    if done == nsteps:
+                        last = outs
+                    del outs
                     if submitted < nsteps:
                         inflight.append((pool.submit(step_fn, inputs),
                                          time.perf_counter()))
                         submitted += 1
             finally:
                 pool.shutdown(wait=True)
-            return lat_local
+            return lat_local, last
         while submitted < min(args.pipeline, nsteps):
             fut, dec = client.predict_future("default", inputs)
             inflight.append((fut, dec, time.perf_counter()))
@@ -391,14 +437,17 @@ def main():
         done = 0
         while done < nsteps:
             fut, dec, ts = inflight.pop(0)
-            dec(fut.result(), output_device=out_dev)
+            outs = dec(fut.result(), output_device=out_dev)
             lat_local.append(time.perf_counter() - ts)
             done += 1
+            if done == nsteps:
+                last = outs
+            del outs
             if submitted < nsteps:
                 fut, dec = client.predict_future("default", inputs)
                 inflight.append((fut, dec, time.perf_counter()))
                 submitted += 1
-        return lat_local
+        return lat_local, last
 
     # ---- warmup ------------------------------------------------------
     if args.pipeline > 1:
@@ -410,14 +459,18 @@ def main():
 
     # ---- timed region ------------------------------------------------
     lat = []
+    last_outs = None
     t0 = time.perf_counter()
     if args.pipeline > 1:
-        lat = run_pipelined(args.steps)
+        lat, last_outs = run_pipelined(args.steps)
     else:
-        for _ in range(args.steps):
+        for i in range(args.steps):
             s0 = time.perf_counter()
-            dp_step()
+            outs = dp_step()
             lat.append(time.perf_counter() - s0)
+            if i == args.steps - 1:
+                last_outs = outs
+            del outs
     sync()
     t1 = time.perf_counter()
 
@@ -434,6 +487,9 @@ def main():
     lat.sort()
     p50_ms = statistics.median(lat) * 1e3
     p99_ms = lat[min(len(lat) - 1, int(0.99 * len(lat)))] * 1e3
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(last_outs, args.dump_outputs)
 
     if rank == 0:
         result = {

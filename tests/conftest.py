@@ -1,5 +1,7 @@
 import os
+import shutil
 import sys
+import tempfile
 
 import pytest
 
@@ -28,6 +30,21 @@ def _has_gpu():
 @pytest.fixture(scope="session")
 def gpu_available():
     return _has_gpu()
+
+
+@pytest.fixture
+def sock_dir():
+    """Short private directory for unix-socket paths.
+
+    sockaddr_un.sun_path holds 107 bytes, and pytest's tmp_path (base temp
+    dir + user + test name) can exceed that on its own, so sockets get a
+    directory whose length does not depend on the test's name."""
+    base = tempfile.gettempdir()
+    if len(base) > 48:
+        base = "/tmp"
+    path = tempfile.mkdtemp(prefix="mtc", dir=base)
+    yield path
+    shutil.rmtree(path, ignore_errors=True)
 
 
 def pytest_collection_modifyitems(config, items):

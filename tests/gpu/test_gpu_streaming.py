@@ -95,10 +95,10 @@ def test_server_device_streaming_reply_bytes_identical():
         srv.stop()
 
 
-def test_end_to_end_gpu_streaming_predict(tmp_path):
+def test_end_to_end_gpu_streaming_predict(sock_dir):
     """Full turbo round trip with device tensors through both streaming
     paths (client request + server non-identity StreamingReply)."""
-    sock = f"unix://{tmp_path}/stream.sock"
+    sock = f"unix://{sock_dir}/stream.sock"
     with ModelServer(address=sock, raw_predict=True, device=DEV) as srv:
         srv.manager.load(
             "double", Servable(lambda d: {k: v * 2 for k, v in d.items()}),
@@ -178,10 +178,10 @@ def test_receive_side_parse_fallback_non_canonical():
         srv.stop()
 
 
-def test_predict_uses_parsed_receive(tmp_path):
+def test_predict_uses_parsed_receive(sock_dir):
     """turbo.predict(output_device=cuda) end-to-end through the parse-
     ahead path with a multi-tensor response."""
-    sock = f"unix://{tmp_path}/pr.sock"
+    sock = f"unix://{sock_dir}/pr.sock"
     with ModelServer(address=sock, raw_predict=True, device=DEV) as srv:
         srv.manager.load(
             "mix", Servable(lambda d: {
@@ -240,10 +240,10 @@ def test_concurrent_device_streaming():
         srv.stop()
 
 
-def test_sharded_predict_parse_ahead(tmp_path):
+def test_sharded_predict_parse_ahead(sock_dir):
     """predict_sharded with cuda outputs goes through per-shard
     parse-ahead futures; results must match the single-shot path."""
-    sock = f"unix://{tmp_path}/shard_pa.sock"
+    sock = f"unix://{sock_dir}/shard_pa.sock"
     with ModelServer(address=sock, raw_predict=True, device=DEV) as srv:
         srv.manager.load(
             "double", Servable(lambda d: {k: v * 2 for k, v in d.items()}),
@@ -295,11 +295,11 @@ def test_server_request_prospecting():
         srv.stop()
 
 
-def test_server_prospecting_end_to_end_gpu_servable(tmp_path):
+def test_server_prospecting_end_to_end_gpu_servable(sock_dir):
     """ModelServer(device=cuda): full round trip where BOTH directions
     are prospected (request spans H2D'd during receive, response spans
     H2D'd client-side during receive)."""
-    sock = f"unix://{tmp_path}/prospect.sock"
+    sock = f"unix://{sock_dir}/prospect.sock"
     with ModelServer(address=sock, raw_predict=True, device=DEV) as srv:
         srv.manager.load(
             "triple", Servable(lambda d: {k: v * 3 for k, v in d.items()}),
@@ -311,13 +311,13 @@ def test_server_prospecting_end_to_end_gpu_servable(tmp_path):
             assert torch.equal(out["images"], x * 3)
 
 
-def test_echo_model_skips_prospecting(tmp_path):
+def test_echo_model_skips_prospecting(sock_dir):
     """Identity models are served by the all-C++ echo path; the skip_model
     hook must keep their requests off the GPU while still echoing
     correctly on a cuda-device server."""
     from min_tfs_client_amd.server import identity_servable
 
-    sock = f"unix://{tmp_path}/echo_skip.sock"
+    sock = f"unix://{sock_dir}/echo_skip.sock"
     with ModelServer(address=sock, raw_predict=True, device=DEV) as srv:
         srv.manager.load("default", identity_servable(), version=1)
         with TurboPredictClient(sock, backend="native") as c:

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 _ROOT = os.path.dirname(os.path.dirname(
@@ -12,9 +13,11 @@ _ROOT = os.path.dirname(os.path.dirname(
 
 
 @pytest.mark.timeout(300)
-def test_bench_single_rank_contract():
+def test_bench_single_rank_contract(tmp_path):
+    dump = tmp_path / "outs"
     out = subprocess.run(
-        [sys.executable, "bench.py", "--steps", "3", "--warmup", "1"],
+        [sys.executable, "bench.py", "--steps", "3", "--warmup", "1",
+         "--dump-outputs", str(dump)],
         cwd=_ROOT, capture_output=True, text=True, timeout=280)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -32,6 +35,39 @@ def test_bench_single_rank_contract():
     assert r["value"] > 0 and r["ms_per_step"] > 0
     assert r["config"]["global_batch"] == 32
     assert r["config"]["parallelism"] == "dp1"
+    # --dump-outputs: the echo servable returns the seeded inputs, so the
+    # dumped array is known exactly without a second run
+    import bench
+    assert [p.name for p in dump.iterdir()] == ["images.npy"]
+    got = np.load(dump / "images.npy")
+    assert got.dtype == np.float32
+    want = bench.make_inputs("resnet50", "cpu")["images"].numpy()
+    assert np.array_equal(got, want)
+
+
+def test_bench_full_flag_accepted():
+    out = subprocess.run(
+        [sys.executable, "bench.py", "--full", "--help"],
+        cwd=_ROOT, capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert "--full" in out.stdout and "--dump-outputs" in out.stdout
+
+
+def test_dump_outputs_formats_and_budget(tmp_path, monkeypatch):
+    import bench
+    import torch
+    monkeypatch.setattr(bench, "_DUMP_BUDGET_BYTES", 4096)
+    outs = {"ids": torch.arange(6, dtype=torch.int32).reshape(2, 3),
+            "half": torch.ones(4, dtype=torch.bfloat16),
+            "big": torch.arange(5000, dtype=torch.float32)}
+    bench.dump_outputs(outs, str(tmp_path))
+    ids = np.load(tmp_path / "ids.npy")
+    assert ids.dtype == np.float64 and ids.shape == (2, 3)
+    assert np.load(tmp_path / "half.npy").dtype == np.float32
+    big = np.load(tmp_path / "big.npy")
+    assert big.nbytes <= 4096 // 3 and np.all(np.diff(big) > 0)
+    bench.dump_outputs(outs, str(tmp_path / "again"))
+    assert np.array_equal(big, np.load(tmp_path / "again" / "big.npy"))
 
 
 @pytest.mark.timeout(300)

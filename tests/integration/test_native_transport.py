@@ -150,8 +150,8 @@ def test_native_client_deadline(grpcio_echo_server):
 # native <-> native
 # ---------------------------------------------------------------------------
 
-def test_native_pair_unix_socket(tmp_path):
-    sock = f"unix://{tmp_path}/t.sock"
+def test_native_pair_unix_socket(sock_dir):
+    sock = f"unix://{sock_dir}/t.sock"
     srv = T.GrpcServer(sock, 4)
     srv.register_handler("/t.S/Echo", lambda v: bytes(v))
     addr = srv.start()

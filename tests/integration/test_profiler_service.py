@@ -16,8 +16,8 @@ from min_tfs_client_amd.wire.grpc_stubs import ProfilerServiceStub
 
 @pytest.mark.parametrize("raw", [True, False],
                          ids=["native-transport", "grpcio"])
-def test_profile_and_monitor(raw, tmp_path):
-    addr = f"unix://{tmp_path}/prof.sock" if raw else "127.0.0.1:0"
+def test_profile_and_monitor(raw, sock_dir):
+    addr = f"unix://{sock_dir}/prof.sock" if raw else "127.0.0.1:0"
     with ModelServer(address=addr, raw_predict=raw,
                      transport="native" if raw else "grpcio") as srv:
         srv.manager.load("m", identity_servable(), version=1)

@@ -87,8 +87,8 @@ def test_output_filter_duplicate_message():
 
 @pytest.mark.parametrize("raw", [True, False],
                          ids=["native-raw", "proto-servicer"])
-def test_end_to_end_alias_error(raw, tmp_path):
-    addr = f"unix://{tmp_path}/sig_{raw}.sock" if raw \
+def test_end_to_end_alias_error(raw, sock_dir):
+    addr = f"unix://{sock_dir}/sig_{raw}.sock" if raw \
         else "127.0.0.1:0"
     with ModelServer(address=addr, raw_predict=raw) as srv:
         srv.manager.load("sigmodel", _servable(), version=1)

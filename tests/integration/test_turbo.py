@@ -83,8 +83,8 @@ def test_turbo_client_against_proto_server():
             assert torch.equal(out["x"], x)
 
 
-def test_turbo_unix_socket(tmp_path):
-    sock = f"unix://{tmp_path}/turbo.sock"
+def test_turbo_unix_socket(sock_dir):
+    sock = f"unix://{sock_dir}/turbo.sock"
     with ModelServer(address=sock, raw_predict=True) as srv:
         srv.manager.load("default", identity_servable(), version=1)
         with TurboPredictClient(sock) as client:

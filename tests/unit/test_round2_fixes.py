@@ -151,11 +151,11 @@ def test_reload_factory_fallback_scans_versions(tmp_path):
 # native server multi-listener (--grpc_socket_path analogue)
 # ---------------------------------------------------------------------------
 
-def test_native_server_extra_unix_listener(tmp_path):
+def test_native_server_extra_unix_listener(sock_dir):
     pytest.importorskip("min_tfs_client_amd._transport")
     from min_tfs_client_amd import _transport as T
     srv = T.GrpcServer("127.0.0.1:0", 2)
-    sock = f"unix://{tmp_path}/extra.sock"
+    sock = f"unix://{sock_dir}/extra.sock"
     srv.add_address(sock)
     srv.register_handler("/t.S/Echo", lambda v: bytes(v))
     tcp_addr = srv.start()
