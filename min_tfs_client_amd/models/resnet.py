@@ -8,6 +8,8 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
+from ..preprocess import IMAGENET_MEAN, IMAGENET_STD, ImagePreprocess
+
 
 class Bottleneck(nn.Module):
     expansion = 4
@@ -74,10 +76,21 @@ def resnet50(num_classes: int = 1000) -> ResNet:
 
 
 def resnet50_servable(device: str = "cpu", dtype=torch.float32,
-                      seed: int = 0):
-    """ResNet-50 Servable: input alias "images" (N,3,224,224), output
-    "logits" (N,1000)."""
+                      seed: int = 0, input_format: str = "float_nchw"):
+    """ResNet-50 Servable: input alias "images", output "logits" (N,1000).
+
+    ``input_format="float_nchw"`` (default): "images" is DT_FLOAT
+    (N,3,224,224), already normalized by the client.
+    ``input_format="uint8_nhwc"``: "images" is DT_UINT8 (N,224,224,3) raw
+    pixels — a quarter of the wire and H2D bytes; the server applies the
+    ImageNet normalization and NHWC->NCHW in one fused kernel
+    (``preprocess.ImagePreprocess``) before the model."""
     from ..server import Servable
+
+    if input_format not in ("float_nchw", "uint8_nhwc"):
+        raise ValueError(
+            f"input_format must be 'float_nchw' or 'uint8_nhwc', got "
+            f"{input_format!r}")
 
     torch.manual_seed(seed)
     model = resnet50().to(device=device, dtype=dtype).eval()
@@ -87,15 +100,26 @@ def resnet50_servable(device: str = "cpu", dtype=torch.float32,
         x = inputs["images"]
         if not isinstance(x, torch.Tensor):
             x = torch.as_tensor(x)
+        # a no-op (same tensor) when preprocessing already produced
+        # device/dtype
         x = x.to(device=device, dtype=dtype)
-        return {"logits": model(x).float()}
+        return {"logits": s.module(x).float()}
 
+    if input_format == "uint8_nhwc":
+        images_sig = (4, [-1, 224, 224, 3])                 # DT_UINT8
+        preprocess = {"images": ImagePreprocess(
+            IMAGENET_MEAN, IMAGENET_STD, out_dtype=dtype, layout="nchw",
+            device=device)}
+    else:
+        images_sig = (1, [-1, 3, 224, 224])                 # DT_FLOAT
+        preprocess = None
     s = Servable(
         fn,
         signature={
             "method_name": "tensorflow/serving/predict",
-            "inputs": {"images": (1, [-1, 3, 224, 224])},   # DT_FLOAT
+            "inputs": {"images": images_sig},
             "outputs": {"logits": (1, [-1, 1000])},
-        })
+        },
+        preprocess=preprocess)
     s.module = model
     return s

@@ -7,6 +7,7 @@ to eager PyTorch, so a passing GPU test means the HIP path actually ran.
 """
 from __future__ import annotations
 
+import functools
 from typing import Optional
 
 try:
@@ -71,6 +72,91 @@ def quantize_q8(tensor, scale, zero_point=0.0):
 
 def dequantize_q8(tensor, scale, zero_point=0.0):
     return require_native().dequantize_q8(tensor, scale, zero_point)
+
+
+def normalization_constants(mean, std, pixel_scale=1.0 / 255.0):
+    """Per-channel ``(scale, bias)`` lists for :func:`image_u8_to_float`.
+
+    ``scale_c = float32(pixel_scale / std_c)`` and ``bias_c =
+    float32(-mean_c / std_c)``: computed in Python double, then rounded once
+    to fp32 (the returned floats are exactly those fp32 values)."""
+    scale, bias = _normalization_constants(
+        tuple(float(m) for m in mean), tuple(float(s) for s in std),
+        float(pixel_scale))
+    return list(scale), list(bias)
+
+
+@functools.lru_cache(maxsize=64)
+def _normalization_constants(mean, std, pixel_scale):
+    # cached: a serving process applies the same few constants to every
+    # request, and the kernel itself runs in microseconds
+    import numpy as np
+
+    if len(mean) != len(std):
+        raise ValueError(
+            f"mean has {len(mean)} entries but std has {len(std)}")
+    if any(s == 0.0 for s in std):
+        raise ValueError("std must be non-zero for every channel")
+    scale = tuple(float(np.float32(pixel_scale / s)) for s in std)
+    bias = tuple(float(np.float32(-m / s)) for m, s in zip(mean, std))
+    return scale, bias
+
+
+def image_u8_to_float(tensor, mean, std, out_dtype=None, layout="nchw",
+                      pixel_scale=1.0 / 255.0):
+    """Fused uint8 image ingest: dequantize + per-channel normalize (+ NHWC
+    -> NCHW) of a contiguous ``[N,H,W,C]`` uint8 tensor, ``C`` in 1..4.
+
+        y[n,c,h,w] = out_dtype(float(x[n,h,w,c]) * scale_c + bias_c)
+
+    with ``(scale, bias) = normalization_constants(mean, std, pixel_scale)``,
+    an unfused fp32 multiply then add, and unsigned bytes (200 is 200.0).
+    The result is bit-identical to the eager expression
+    ``(x.permute(0,3,1,2).float() * scale.view(1,C,1,1) +
+    bias.view(1,C,1,1)).to(out_dtype)``; it can differ from
+    ``(x/255 - mean)/std`` by a few ulp, because the constants are folded
+    before the pixel is touched.
+
+    Device tensors run the gfx950 kernel (one pass, no eager fallback);
+    CPU tensors use the eager expression, so CPU-only servers work too.
+    ``layout`` selects the output layout, ``"nchw"`` or ``"nhwc"``. Invalid
+    arguments raise ``ValueError`` on both paths."""
+    if out_dtype is None:
+        out_dtype = torch.float32
+    if layout not in ("nchw", "nhwc"):
+        raise ValueError(f"layout must be 'nchw' or 'nhwc', got {layout!r}")
+    if out_dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError(
+            f"out_dtype must be float32, bfloat16 or float16, got {out_dtype}")
+    if not isinstance(tensor, torch.Tensor):
+        raise ValueError("image_u8_to_float expects a torch tensor")
+    if tensor.dtype != torch.uint8:
+        raise ValueError(
+            f"image_u8_to_float expects uint8 pixels, got {tensor.dtype}")
+    if tensor.dim() != 4:
+        raise ValueError(
+            f"image_u8_to_float expects [N,H,W,C], got rank {tensor.dim()}")
+    if not tensor.is_contiguous():
+        raise ValueError("image_u8_to_float expects a contiguous tensor")
+    C = int(tensor.shape[3])
+    if not 1 <= C <= 4:
+        raise ValueError(f"image_u8_to_float supports 1..4 channels, got {C}")
+    if len(mean) != C or len(std) != C:
+        raise ValueError(
+            f"mean/std need {C} entries (one per channel), got "
+            f"{len(mean)}/{len(std)}")
+    scale, bias = normalization_constants(mean, std, pixel_scale)
+    if tensor.is_cuda:
+        return require_native().u8_nhwc_normalize(
+            tensor, scale, bias, out_dtype, layout == "nchw")
+    s = torch.tensor(scale, dtype=torch.float32)
+    b = torch.tensor(bias, dtype=torch.float32)
+    if layout == "nchw":
+        x = tensor.permute(0, 3, 1, 2).float()
+        y = x * s.view(1, C, 1, 1) + b.view(1, C, 1, 1)
+    else:
+        y = tensor.float() * s.view(1, 1, 1, C) + b.view(1, 1, 1, C)
+    return y.to(out_dtype).contiguous()
 
 
 def pack_tensor_proto(tensor):

@@ -68,16 +68,29 @@ class Servable:
     ``fn`` may return numpy arrays or torch tensors. ``signature`` describes
     inputs/outputs for GetModelMetadata: {"inputs": {alias: (dtype_enum,
     shape)}, "outputs": {...}, "method_name": str}.
+
+    ``preprocess`` is an optional ``{alias: callable}``: each callable is
+    applied to its alias' input before ``fn`` (see ``preprocess.py``);
+    aliases without an entry pass through untouched and the caller's dict
+    is never mutated. A callable that raises ``ValueError`` is reported as
+    INVALID_ARGUMENT by every transport.
     """
 
     def __init__(self, fn: Callable[[Dict[str, np.ndarray]], Dict[str, np.ndarray]],
                  signature: Optional[dict] = None,
-                 signature_name: str = "serving_default"):
+                 signature_name: str = "serving_default",
+                 preprocess: Optional[Dict[str, Callable]] = None):
         self.fn = fn
         self.signature = signature or {}
         self.signature_name = signature_name
+        self.preprocess = dict(preprocess) if preprocess else {}
 
     def __call__(self, inputs: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
+        if self.preprocess:
+            inputs = dict(inputs)
+            for alias, pre in self.preprocess.items():
+                if alias in inputs:
+                    inputs[alias] = pre(inputs[alias])
         return self.fn(inputs)
 
 

@@ -4,6 +4,8 @@
 Run under rocprofv3 for per-kernel hardware stats:
   cd /tmp && rocprofv3 --kernel-trace --stats -d gpurun_out/prof -- \
       python tools/profile_kernels.py
+
+``--only-u8`` runs just the fused uint8 image-ingest section.
 """
 import json
 import os
@@ -35,6 +37,39 @@ def report(name, ms, bytes_moved):
     gbps = bytes_moved / 1e9 / (ms / 1e3)
     print(json.dumps({"kernel": name, "ms": round(ms, 4),
                       "GB_s": round(gbps, 1)}))
+
+
+def profile_u8_normalize(dev="cuda:0", op=None):
+    """Fused uint8 image ingest (u8_nhwc_normalize): uint8 NHWC -> normalized
+    NCHW, vs the eager chain it replaces (permute -> float -> mul -> add ->
+    to -> contiguous). Interleaved rounds in one process; the median round
+    is reported. ``op`` overrides the fused callable (kernel variants)."""
+    op = op or ops.image_u8_to_float
+    mean, std = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+    scale, bias = ops.normalization_constants(mean, std)
+    u8 = torch.randint(0, 256, (32, 224, 224, 3), device=dev,
+                       dtype=torch.uint8)
+    s_dev = torch.tensor(scale, device=dev).view(1, 3, 1, 1)
+    b_dev = torch.tensor(bias, device=dev).view(1, 3, 1, 1)
+    for tag, od in (("bf16", torch.bfloat16), ("f32", torch.float32)):
+        def fused():
+            return op(u8, mean, std, out_dtype=od)
+
+        def eager():
+            return (u8.permute(0, 3, 1, 2).float() * s_dev
+                    + b_dev).to(od).contiguous()
+
+        assert torch.equal(fused(), eager())
+        nbytes = u8.numel() * (1 + torch.empty((), dtype=od).element_size())
+        rounds = [(time_kernel(fused, reps=200, warmup=20),
+                   time_kernel(eager, reps=200, warmup=20))
+                  for _ in range(5)]
+        ms_fused = sorted(r[0] for r in rounds)[2]
+        ms_eager = sorted(r[1] for r in rounds)[2]
+        report(f"u8_nhwc_normalize_32x224x224x3_{tag}_nchw", ms_fused, nbytes)
+        report(f"torch_eager_u8_normalize_chain_{tag}_nchw", ms_eager, nbytes)
+        print(json.dumps({"kernel": f"u8_nhwc_normalize_{tag}_speedup",
+                          "eager_over_fused": round(ms_eager / ms_fused, 2)}))
 
 
 def main():
@@ -80,6 +115,8 @@ def main():
     ms = time_kernel(lambda: ops.nchw_to_nhwc(x, torch.float32))
     report("nchw_nhwc_smallC_256x3x224x224_bf16f32", ms, nbytes)
 
+    profile_u8_normalize(dev)
+
     # --- quantize ----------------------------------------------------------
     x = torch.randn(128 << 20, device=dev)
     nbytes = x.numel() * (4 + 1)
@@ -88,4 +125,8 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if "--only-u8" in sys.argv[1:]:
+        assert torch.cuda.is_available()
+        profile_u8_normalize()
+    else:
+        main()
