@@ -88,10 +88,29 @@ def bert_base() -> BertEncoder:
     return BertEncoder()
 
 
-def bert_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0):
-    """BERT-base Servable: inputs "input_ids"/"attention_mask" int32,
-    outputs "last_hidden_state" + "pooled_output"."""
+def bert_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
+                  output_format: str = "hidden",
+                  normalize_embedding: bool = True):
+    """BERT-base Servable: inputs "input_ids"/"attention_mask" int32.
+
+    ``output_format="hidden"`` (default): outputs "last_hidden_state"
+    (B,S,768) + "pooled_output" (B,768), both DT_FLOAT.
+    ``output_format="sentence_embedding"``: the only output is
+    "sentence_embedding", DT_FLOAT (B,768) — the mean of the hidden state
+    over the positions ``attention_mask`` keeps (all positions when the mask
+    is absent), L2-normalized when ``normalize_embedding``. It is S x fewer
+    response bytes, pooled on the server by one fused kernel
+    (``ops.masked_mean_pool``) straight from the model's own dtype; a pooled
+    row is deterministic and ignores masked positions."""
+    from .. import ops
     from ..server import Servable
+
+    if output_format not in ("hidden", "sentence_embedding"):
+        raise ValueError(
+            f"output_format must be 'hidden' or 'sentence_embedding', got "
+            f"{output_format!r}")
+    embed = output_format == "sentence_embedding"
+    normalize_embedding = bool(normalize_embedding)
 
     torch.manual_seed(seed)
     model = bert_base().to(device=device, dtype=dtype).eval()
@@ -107,18 +126,25 @@ def bert_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0):
             if not isinstance(mask, torch.Tensor):
                 mask = torch.as_tensor(mask)
             mask = mask.to(device=device)
-        hidden, pooled = model(ids, mask)
+        hidden, pooled = s.module(ids, mask)
+        if embed:
+            return {"sentence_embedding": ops.masked_mean_pool(
+                hidden.contiguous(), mask, normalize_embedding)}
         return {"last_hidden_state": hidden.float(),
                 "pooled_output": pooled.float()}
 
+    if embed:
+        outputs = {"sentence_embedding": (1, [-1, 768])}
+    else:
+        outputs = {"last_hidden_state": (1, [-1, -1, 768]),
+                   "pooled_output": (1, [-1, 768])}
     s = Servable(
         fn,
         signature={
             "method_name": "tensorflow/serving/predict",
             "inputs": {"input_ids": (3, [-1, -1]),
                        "attention_mask": (3, [-1, -1])},  # DT_INT32
-            "outputs": {"last_hidden_state": (1, [-1, -1, 768]),
-                        "pooled_output": (1, [-1, 768])},
+            "outputs": outputs,
         })
     s.module = model
     return s

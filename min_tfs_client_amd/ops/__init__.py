@@ -159,6 +159,73 @@ def image_u8_to_float(tensor, mean, std, out_dtype=None, layout="nchw",
     return y.to(out_dtype).contiguous()
 
 
+def masked_mean_pool(hidden, mask=None, normalize=False):
+    """Fused masked mean-pool head: ``[B,S,H]`` hidden state (f32, bf16 or
+    f16, contiguous) -> fp32 ``[B,H]``, one vector per sequence.
+
+        cnt_b = number of s with mask[b,s] != 0
+        y_bh  = (sum of float(hidden[b,s,h]) over kept s) / max(cnt_b, 1)
+        normalize:  y_bh = y_bh / max(sqrt(sum_h y_bh**2), 1e-12)
+
+    fp32 accumulation, IEEE division and square root (``F.normalize``
+    semantics). Masked positions are selected out, never multiplied in, so a
+    NaN or Inf there does not reach the output; a row with nothing kept (or
+    ``S == 0``) is zeros. The result is deterministic: the same input gives
+    bit-identical output on every run.
+
+    ``mask`` is ``[B,S]`` of an integer or bool dtype on the device of
+    ``hidden``; non-zero keeps the position and ``None`` keeps all. int32,
+    uint8 and bool go to the kernel as they are, other integer dtypes are
+    reduced with ``mask != 0`` first.
+
+    Device tensors run the gfx950 kernels (the hidden state is read once, no
+    eager fallback); CPU tensors use an eager expression with the same
+    semantics, so CPU-only servers work too. Invalid arguments raise
+    ``ValueError`` on both paths."""
+    if not isinstance(hidden, torch.Tensor):
+        raise ValueError("masked_mean_pool expects a torch tensor")
+    if hidden.dim() != 3:
+        raise ValueError(
+            f"masked_mean_pool expects [B,S,H], got rank {hidden.dim()}")
+    if hidden.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError(
+            "masked_mean_pool expects float32, bfloat16 or float16, got "
+            f"{hidden.dtype}")
+    if not hidden.is_contiguous():
+        raise ValueError("masked_mean_pool expects a contiguous tensor")
+    B, S, H = (int(d) for d in hidden.shape)
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor):
+            raise ValueError("masked_mean_pool expects a torch tensor mask")
+        if tuple(mask.shape) != (B, S):
+            raise ValueError(
+                f"mask must have shape {[B, S]}, got {list(mask.shape)}")
+        if mask.is_floating_point() or mask.is_complex():
+            raise ValueError(
+                f"mask must be an integer or bool tensor, got {mask.dtype}")
+        if mask.device != hidden.device:
+            raise ValueError(
+                f"mask is on {mask.device} but hidden is on {hidden.device}")
+        if mask.dtype not in (torch.int32, torch.uint8, torch.bool):
+            mask = mask != 0   # e.g. int64: 1 << 32 is still "keep"
+        mask = mask.contiguous()
+    if hidden.is_cuda:
+        return require_native().masked_mean_pool(hidden, mask, bool(normalize))
+    x = hidden.float()
+    if mask is None:
+        total = x.sum(1)
+        count = torch.full((B, 1), max(S, 1), dtype=torch.float32)
+    else:
+        keep = mask != 0
+        total = torch.where(keep[..., None], x, torch.zeros((), dtype=x.dtype)
+                            ).sum(1)
+        count = keep.sum(1, keepdim=True).clamp(min=1).float()
+    y = total / count
+    if normalize:
+        y = y / y.norm(dim=1, keepdim=True).clamp(min=1e-12)
+    return y.contiguous()
+
+
 def pack_tensor_proto(tensor):
     """Device tensor -> python TensorProto message (for the non-turbo
     client path): native D2H pipeline for the payload, proto wrapper around

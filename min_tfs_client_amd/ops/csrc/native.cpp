@@ -29,6 +29,9 @@ at::Tensor nhwc_to_nchw(const at::Tensor& in, at::ScalarType out_dtype);
 at::Tensor u8_nhwc_normalize(const at::Tensor& in, std::vector<double> scale,
                              std::vector<double> bias,
                              at::ScalarType out_dtype, bool out_nchw);
+at::Tensor masked_mean_pool(const at::Tensor& hidden,
+                            const c10::optional<at::Tensor>& mask,
+                            bool normalize);
 at::Tensor quantize_q8(const at::Tensor& in, double scale, double zp);
 at::Tensor dequantize_q8(const at::Tensor& in, double scale, double zp);
 void copy_device_to_host_ptr(const at::Tensor& src, void* dst, size_t n,
@@ -624,6 +627,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("u8_nhwc_normalize", &mi355x::u8_nhwc_normalize, py::arg("input"),
         py::arg("scale"), py::arg("bias"), py::arg("out_dtype"),
         py::arg("out_nchw") = true);
+  m.def("masked_mean_pool", &mi355x::masked_mean_pool, py::arg("hidden"),
+        py::arg("mask") = py::none(), py::arg("normalize") = false);
   m.def("quantize_q8", &mi355x::quantize_q8, py::arg("input"),
         py::arg("scale"), py::arg("zero_point") = 0.0);
   m.def("dequantize_q8", &mi355x::dequantize_q8, py::arg("input"),

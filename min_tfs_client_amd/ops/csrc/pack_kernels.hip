@@ -11,6 +11,8 @@
 //  * affine int8 quantize/dequantize (the "cast/quantize" pack stage),
 //  * fused uint8 image ingest: dequantize + per-channel normalize + NCHW
 //    (server-side preprocessing, so clients ship 1 byte per pixel value),
+//  * fused masked mean-pool (+ L2 normalize) head: [B,S,H] hidden state ->
+//    fp32 [B,H] sentence embeddings, so responses ship S x fewer bytes,
 // plus the host-side staging machinery: pinned double-buffered
 // device->host-buffer copies that overlap DMA with the host-side wire write
 // (the MI355X replacement for the reference's two-slice zero-copy encode,
@@ -508,6 +510,200 @@ __global__ void u8_nhwc_normalize_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// fused masked mean-pool head (+ optional L2 normalize): [B,S,H] -> [B,H]
+// ---------------------------------------------------------------------------
+// cnt_b  = #{s : mask[b,s] != 0}
+// sum_bh = sum over kept s of float(hidden[b,s,h])   (fp32, SELECT: a masked
+//          row is never loaded, so NaN/Inf there cannot reach the output)
+// y_bh   = sum_bh / float(max(cnt_b, 1))
+// normalize: y_bh /= max(sqrt(sum_h y_bh^2), 1e-12f)  (F.normalize semantics)
+//
+// Division and square root are correctly rounded: `__fdiv_rn` is an IEEE
+// divide here and `sqrtf` an IEEE square root (hipcc's default
+// -fhip-fp32-correctly-rounded-divide-sqrt). `__fsqrt_rn` is NOT used: in
+// this toolchain it lowers to the native v_sqrt_f32, which is 1 ulp off.
+//
+// Two kernels, always, in this order on the current stream:
+//
+//  1. masked_pool_partial_kernel reads the hidden state once. A work item
+//     is (b, S-slice k, column tile): one 256-thread workgroup, whose 4
+//     waves take rows s = s_begin + wave, +4, ... of the slice; the 64
+//     lanes of a wave span 64 consecutive column vectors of one row (one
+//     contiguous run, 1 KB on the vector path), so the mask test is
+//     wave-uniform and a masked row costs one 4 B load. Rows are unrolled
+//     4 deep per wave to keep 4 loads in flight. The 4 waves' accumulators
+//     are combined through LDS in wave order and the slice's partial sums
+//     go to a [B, nsplit, H] fp32 workspace. No atomics.
+//  2. masked_pool_finalize_kernel: one workgroup per b. It counts the mask
+//     row (integer block reduction), adds the nsplit partials for each h in
+//     slice order, divides, and (normalize) reduces y^2 over the row with a
+//     fixed shuffle tree + LDS, takes the square root and divides again.
+//
+// Every sum has a fixed order that depends only on the shape, so the output
+// is bit-identical from run to run.
+//
+// Paths and thresholds (the tests pin one shape on each side):
+//  * vector path: VEC = 16/sizeof(T) elements per lane (4 f32, 8 bf16/f16),
+//    taken iff the base pointer and H*sizeof(T) are multiples of 16;
+//    otherwise the scalar path, VEC = 1. Column tiles: ceil(H/VEC / 64).
+//  * S split: nsplit = 1 if B*tiles >= kPoolTargetBlocks (1024) or
+//    S <= kPoolMinRows (16); else nsplit = min(ceil(1024 / (B*tiles)),
+//    ceil(S/16)), rows per slice = ceil(S/nsplit), nsplit = ceil(S/rows).
+//  * grid: min(B*nsplit*tiles, 2048) workgroups (grid_for), grid-stride over
+//    work items; the finalize grid is min(B, 2048), grid-stride over b.
+//  * S == 0 or an all-zero mask row: sums are 0 and the count clamps to 1,
+//    so the row is zeros. B == 0 or H == 0 returns without launching.
+constexpr int kPoolBlock = 256;          // 4 waves
+constexpr int kPoolWaves = kPoolBlock / 64;
+constexpr int64_t kPoolTargetBlocks = 1024;
+constexpr int64_t kPoolMinRows = 16;
+
+template <typename CVT, int VEC>
+__device__ __forceinline__ void pool_load(
+    const typename CVT::In* __restrict__ p, typename CVT::In (&v)[VEC]) {
+  if constexpr (VEC == 1) {
+    v[0] = *p;
+  } else {
+    static_assert(sizeof(typename CVT::In) * VEC == 16, "16 B per lane");
+    *reinterpret_cast<int4*>(v) = *reinterpret_cast<const int4*>(p);
+  }
+}
+
+template <typename CVT, int VEC, typename M>
+__global__ void __launch_bounds__(kPoolBlock) masked_pool_partial_kernel(
+    const typename CVT::In* __restrict__ hidden, const M* __restrict__ mask,
+    float* __restrict__ ws, int64_t B, int64_t S, int64_t H, int64_t tiles,
+    int64_t nsplit, int64_t rows_per_split) {
+  using In = typename CVT::In;
+  __shared__ float lds[kPoolWaves - 1][64][VEC];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int64_t items = B * nsplit * tiles;
+  for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+    const int64_t tile = item % tiles;
+    const int64_t k = (item / tiles) % nsplit;
+    const int64_t b = item / (tiles * nsplit);
+    const int64_t col = (tile * 64 + lane) * VEC;
+    // vector path: H % VEC == 0, so col < H implies col + VEC <= H
+    const bool active = col < H;
+    const int64_t s_begin = k * rows_per_split;
+    const int64_t s_end = min(S, s_begin + rows_per_split);
+    const In* row0 = hidden + b * S * H + col;
+    const M* mrow = mask ? mask + b * S : nullptr;
+
+    float acc[VEC];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) acc[e] = 0.f;
+
+    int64_t s = s_begin + wave;
+    for (; s + 3 * kPoolWaves < s_end; s += 4 * kPoolWaves) {
+      bool keep[4];
+      In v[4][VEC];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int64_t su = s + u * kPoolWaves;
+        keep[u] = active && (!mrow || mrow[su] != 0);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (keep[u])
+          pool_load<CVT, VEC>(row0 + (s + u * kPoolWaves) * H, v[u]);
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (keep[u]) {
+#pragma unroll
+          for (int e = 0; e < VEC; ++e) acc[e] += CVT::cvt(v[u][e]);
+        }
+    }
+    for (; s < s_end; s += kPoolWaves) {
+      if (active && (!mrow || mrow[s] != 0)) {
+        In v[VEC];
+        pool_load<CVT, VEC>(row0 + s * H, v);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc[e] += CVT::cvt(v[e]);
+      }
+    }
+
+    // combine the 4 waves in wave order
+    if (wave > 0) {
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) lds[wave - 1][lane][e] = acc[e];
+    }
+    __syncthreads();
+    if (wave == 0 && active) {
+#pragma unroll
+      for (int w = 0; w < kPoolWaves - 1; ++w)
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc[e] += lds[w][lane][e];
+      float* dst = ws + (b * nsplit + k) * H + col;
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) dst[e] = acc[e];
+    }
+    __syncthreads();  // lds is reused by the next work item
+  }
+}
+
+// Sum of `v` over the workgroup, the same value in every thread. Fixed
+// shuffle tree within a wave, then the waves in order: deterministic.
+__device__ __forceinline__ float pool_block_sum(float v, float* red) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  __syncthreads();  // red may still be read from a previous call
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  float total = red[0];
+#pragma unroll
+  for (int w = 1; w < kPoolWaves; ++w) total += red[w];
+  return total;
+}
+
+template <typename M>
+__global__ void __launch_bounds__(kPoolBlock) masked_pool_finalize_kernel(
+    const float* __restrict__ ws, const M* __restrict__ mask,
+    float* __restrict__ out, int64_t B, int64_t S, int64_t H,
+    int64_t nsplit, bool normalize) {
+  __shared__ float red[kPoolWaves];
+  __shared__ int cnt_red[kPoolWaves];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
+    int64_t cnt = S;
+    if (mask) {
+      int c = 0;
+      for (int64_t s = threadIdx.x; s < S; s += kPoolBlock)
+        c += mask[b * S + s] != 0;
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+      __syncthreads();  // cnt_red may still be read for the previous b
+      if (lane == 0) cnt_red[wave] = c;
+      __syncthreads();
+      cnt = 0;
+#pragma unroll
+      for (int w = 0; w < kPoolWaves; ++w) cnt += cnt_red[w];
+    }
+    const float denom = float(max(cnt, int64_t(1)));
+    const float* part = ws + b * nsplit * H;
+    float* y = out + b * H;
+    float sq = 0.f;
+    for (int64_t h = threadIdx.x; h < H; h += kPoolBlock) {
+      float sum = part[h];
+      for (int64_t k = 1; k < nsplit; ++k) sum += part[k * H + h];
+      const float mean = __fdiv_rn(sum, denom);
+      y[h] = mean;
+      sq += mean * mean;
+    }
+    if (normalize) {  // uniform across the grid
+      const float norm = fmaxf(sqrtf(pool_block_sum(sq, red)), 1e-12f);
+      // each thread re-reads only what it wrote itself
+      for (int64_t h = threadIdx.x; h < H; h += kPoolBlock)
+        y[h] = __fdiv_rn(y[h], norm);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // launch helpers
 // ---------------------------------------------------------------------------
 
@@ -779,6 +975,87 @@ at::Tensor u8_nhwc_normalize(const at::Tensor& in, std::vector<double> scale,
   if (out_dtype == at::kFloat) by_channels(IdF32{});
   else if (out_dtype == at::kBFloat16) by_channels(F32ToBf16{});
   else by_channels(F32ToF16{});
+  HIP_CHECK(hipGetLastError());
+  return out;
+}
+
+// Fused masked mean-pool (+ optional L2 normalize) of a [B,S,H] hidden state
+// into fp32 [B,H]; see the kernel section for semantics, paths and
+// thresholds. `mask` is [B,S] int32 or uint8/bool (non-zero keeps), or
+// nullopt to keep every position.
+at::Tensor masked_mean_pool(const at::Tensor& hidden,
+                            const c10::optional<at::Tensor>& mask,
+                            bool normalize) {
+  TORCH_CHECK(hidden.is_cuda() && hidden.dim() == 3 && hidden.is_contiguous(),
+              "masked_mean_pool expects a contiguous device tensor [B,S,H]");
+  const auto id = hidden.scalar_type();
+  TORCH_CHECK(id == at::kFloat || id == at::kBFloat16 || id == at::kHalf,
+              "masked_mean_pool: hidden must be f32, bf16 or f16");
+  const int64_t B = hidden.size(0), S = hidden.size(1), H = hidden.size(2);
+  const void* mptr = nullptr;
+  int mask_bytes = 0;
+  if (mask.has_value()) {
+    const at::Tensor& m = *mask;
+    const auto md = m.scalar_type();
+    TORCH_CHECK(m.is_cuda() && m.device() == hidden.device() &&
+                m.dim() == 2 && m.size(0) == B && m.size(1) == S &&
+                m.is_contiguous(),
+                "masked_mean_pool: mask must be a contiguous [B,S] tensor on "
+                "the device of hidden");
+    TORCH_CHECK(md == at::kInt || md == at::kByte || md == at::kBool,
+                "masked_mean_pool: mask must be int32, uint8 or bool");
+    mask_bytes = md == at::kInt ? 4 : 1;
+    mptr = m.const_data_ptr();
+  }
+  auto out = at::empty({B, H}, hidden.options().dtype(at::kFloat));
+  if (B == 0 || H == 0) return out;  // zero grid: never launch
+
+  const int64_t esize = hidden.element_size();
+  const bool vec =
+      (reinterpret_cast<uintptr_t>(hidden.const_data_ptr()) & 15) == 0 &&
+      (H * esize) % 16 == 0;
+  const int64_t vec_elems = vec ? 16 / esize : 1;
+  const int64_t tiles = (H / vec_elems + 63) / 64;  // vec: H % vec_elems == 0
+  int64_t nsplit = 1;
+  if (B * tiles < kPoolTargetBlocks && S > kPoolMinRows) {
+    nsplit = std::min((kPoolTargetBlocks + B * tiles - 1) / (B * tiles),
+                      (S + kPoolMinRows - 1) / kPoolMinRows);
+  }
+  const int64_t rows_per_split = (S + nsplit - 1) / nsplit;
+  if (rows_per_split > 0) nsplit = (S + rows_per_split - 1) / rows_per_split;
+  auto ws = at::empty({B, nsplit, H}, out.options());
+
+  const int grid1 = grid_for(B * nsplit * tiles * kPoolBlock, kPoolBlock);
+  const int grid2 = grid_for(B * kPoolBlock, kPoolBlock);
+  auto launch = [&](auto cvt_tag, auto vec_tag, auto mask_tag) {
+    using CVT = decltype(cvt_tag);
+    using M = decltype(mask_tag);
+    const M* mp = static_cast<const M*>(mptr);
+    hipLaunchKernelGGL(
+        (masked_pool_partial_kernel<CVT, decltype(vec_tag)::value, M>),
+        dim3(grid1), dim3(kPoolBlock), 0, current_stream(),
+        reinterpret_cast<const typename CVT::In*>(hidden.const_data_ptr()),
+        mp, ws.data_ptr<float>(), B, S, H, tiles, nsplit, rows_per_split);
+    HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(masked_pool_finalize_kernel<M>, dim3(grid2),
+                       dim3(kPoolBlock), 0, current_stream(),
+                       ws.data_ptr<float>(), mp, out.data_ptr<float>(), B, S,
+                       H, nsplit, normalize);
+  };
+  auto by_mask = [&](auto cvt_tag, auto vec_tag) {
+    if (mask_bytes == 4) launch(cvt_tag, vec_tag, int32_t{});
+    else launch(cvt_tag, vec_tag, uint8_t{});  // also the mask-less case
+  };
+  auto by_vec = [&](auto cvt_tag) {
+    using In = typename decltype(cvt_tag)::In;
+    if (vec)
+      by_mask(cvt_tag, std::integral_constant<int, 16 / int(sizeof(In))>{});
+    else
+      by_mask(cvt_tag, std::integral_constant<int, 1>{});
+  };
+  if (id == at::kFloat) by_vec(IdF32{});
+  else if (id == at::kBFloat16) by_vec(Bf16ToF32{});
+  else by_vec(F16ToF32{});
   HIP_CHECK(hipGetLastError());
   return out;
 }

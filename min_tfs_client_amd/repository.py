@@ -15,6 +15,9 @@ On-disk version-directory formats understood by the default loader:
   * ``identity``            — empty marker file -> identity echo servable
   * ``model.json``          — {"family": "resnet50"|"bert_base",
                                "device": ..., "state_dict": "weights.pt"?}
+                               plus optional I/O modes: "input_format"
+                               (resnet50), "output_format" and
+                               "normalize_embedding" (bert_base)
   * ``model.pt``            — TorchScript module (torch.jit.load)
 plus TF-style ``assets.extra/tf_serving_warmup_requests`` (a TFRecord of
 serialized PredictionLog protos — framing per TF's RecordWriter: length,
@@ -159,12 +162,18 @@ def default_loader(name: str, version_dir: str,
             cfg = json.load(f)
         family = cfg.get("family")
         device = cfg.get("device", device)
+        # optional I/O-mode keys go to the servable factory only when
+        # present; an unknown value is the factory's ValueError
         if family == "resnet50":
             from .models import resnet50_servable
-            servable = resnet50_servable(device)
+            modes = {k: cfg[k] for k in ("input_format",) if k in cfg}
+            servable = resnet50_servable(device, **modes)
         elif family == "bert_base":
             from .models import bert_servable
-            servable = bert_servable(device)
+            modes = {k: cfg[k]
+                     for k in ("output_format", "normalize_embedding")
+                     if k in cfg}
+            servable = bert_servable(device, **modes)
         elif family == "identity":
             servable = identity_servable()
         else:
