@@ -41,6 +41,7 @@
 
 #include "h2core.h"
 #include "hpack.h"
+#include "sharded.h"
 #include "staging.h"
 #include "wire.h"
 
@@ -1592,6 +1593,7 @@ class GrpcChannel {
       }
       id = next_stream_;
       next_stream_ += 2;
+      streams_started_.fetch_add(1, std::memory_order_relaxed);
       pending_[id] = p;
       conn_->open_send_stream(id);
       // HEADERS must hit the wire in stream-id order: send under mu_
@@ -1730,6 +1732,12 @@ class GrpcChannel {
     return r;
   }
 
+  // streams opened on this channel so far (read-only diagnostic: shows
+  // how requests spread over a multi-channel client)
+  uint64_t streams_started() const {
+    return streams_started_.load(std::memory_order_relaxed);
+  }
+
   Buf wait(uint32_t id, double timeout_s) {
     std::shared_ptr<Pending> p;
     {
@@ -1797,6 +1805,7 @@ class GrpcChannel {
   std::condition_variable cv_;
   std::unordered_map<uint32_t, std::shared_ptr<Pending>> pending_;
   uint32_t next_stream_ = 1;
+  std::atomic<uint64_t> streams_started_{0};
 
   std::string make_request_headers(const std::string& path,
                                    double timeout_s) {
@@ -1988,6 +1997,326 @@ class GrpcChannel {
     }
   }
 };
+
+// ===========================================================================
+// Sharded Predict: one native call per logical request
+// ===========================================================================
+// TurboPredictClient.predict_sharded used to orchestrate every shard from
+// python: per shard one serialize call, one stream synchronize, one
+// thread-pool job and one wait, all trading the GIL with the other
+// in-flight requests. Here the whole request runs behind ONE GIL release:
+// plan the shards (sharded.h), synchronize the producer stream once, send
+// the shards in parallel (caller thread + persistent sender pool), wait
+// for every reply and concatenate the device-parsed outputs. No new
+// socket, framing or receive code: only start_call_streaming / wait /
+// wait_parsed are orchestrated.
+
+inline int scalar_to_tf_dtype(at::ScalarType t) {
+  switch (t) {
+    case at::kFloat: return 1;
+    case at::kDouble: return 2;
+    case at::kInt: return 3;
+    case at::kByte: return 4;
+    case at::kShort: return 5;
+    case at::kChar: return 6;
+    case at::kComplexFloat: return 8;
+    case at::kLong: return 9;
+    case at::kBool: return 10;
+    case at::kBFloat16: return 14;
+    case at::kUInt16: return 17;
+    case at::kComplexDouble: return 18;
+    case at::kHalf: return 19;
+    case at::kUInt32: return 22;
+    case at::kUInt64: return 23;
+    default:
+      throw std::invalid_argument("unsupported torch dtype for TensorProto");
+  }
+}
+
+// Persistent pool of tfsshard::kSenderPoolSize threads that run blocking
+// shard sends. Created lazily on first use, never per call; its threads
+// never touch python. shutdown() takes the threads out under the lock and
+// joins them outside it (queued jobs are drained first); a later submit
+// simply starts a fresh set, so one client's close() cannot strand
+// another client's request.
+class SenderPool {
+ public:
+  static SenderPool& instance() {
+    static SenderPool* pool = new SenderPool();  // leaked: immortal
+    return *pool;
+  }
+
+  // false while shutting down: the caller then runs the job itself
+  bool submit(std::function<void()> job) {
+    {
+      std::lock_guard<std::mutex> lk(mu_);
+      if (stopping_) return false;
+      if (threads_.empty())
+        for (int i = 0; i < tfsshard::kSenderPoolSize; ++i)
+          threads_.emplace_back([this] { loop(); });
+      queue_.push_back(std::move(job));
+    }
+    cv_.notify_one();
+    return true;
+  }
+
+  void shutdown() {
+    std::vector<std::thread> threads;
+    {
+      std::lock_guard<std::mutex> lk(mu_);
+      if (threads_.empty()) return;
+      stopping_ = true;
+      threads.swap(threads_);
+    }
+    cv_.notify_all();
+    for (auto& t : threads)
+      if (t.joinable()) t.join();
+    std::lock_guard<std::mutex> lk(mu_);
+    stopping_ = false;
+  }
+
+ private:
+  void loop() {
+    for (;;) {
+      std::function<void()> job;
+      {
+        std::unique_lock<std::mutex> lk(mu_);
+        cv_.wait(lk, [this] { return stopping_ || !queue_.empty(); });
+        if (queue_.empty()) return;  // stopping and drained
+        job = std::move(queue_.front());
+        queue_.pop_front();
+      }
+      job();  // jobs record their own errors; they never throw
+    }
+  }
+
+  std::mutex mu_;
+  std::condition_variable cv_;
+  std::deque<std::function<void()>> queue_;
+  std::vector<std::thread> threads_;
+  bool stopping_ = false;
+};
+
+std::atomic<uint32_t> g_shard_rotation{0};
+
+inline double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(
+             std::chrono::steady_clock::now() - t0)
+      .count();
+}
+
+// Shared between the calling thread and the sender-pool jobs of one
+// request. Every shard is sent by whoever CLAIMS it first: the pool jobs
+// claim theirs when a pool thread picks them up, and the caller — after
+// sending shard 0 — claims whatever is still unclaimed, so a saturated
+// (or stopping) pool delays nothing and cannot deadlock a request.
+struct ShardedCall {
+  struct Shard {
+    tfsshard::ShardPlan plan;
+    std::vector<WireRegion> regions;
+    GrpcChannel* ch = nullptr;
+    std::atomic<bool> claimed{false};
+    bool started = false;
+    uint32_t id = 0;
+    std::exception_ptr err;
+    double send_start_ms = 0.0, send_ms = 0.0;
+  };
+
+  std::string path;
+  double timeout = 0.0;
+  int parse_device = -1;
+  std::chrono::steady_clock::time_point t0;
+  std::vector<Shard> shards;
+  std::mutex m;
+  std::condition_variable cv;
+  size_t sends_pending = 0;
+
+  explicit ShardedCall(size_t n) : shards(n), sends_pending(n) {}
+
+  // true when this thread won the shard and sent it (or recorded its error)
+  bool try_send(size_t i) {
+    Shard& s = shards[i];
+    if (s.claimed.exchange(true)) return false;
+    s.send_start_ms = ms_since(t0);
+    try {
+      s.id = s.ch->start_call_streaming(path, s.plan.skeleton.get(),
+                                        s.plan.size, s.regions,
+                                        timeout, parse_device);
+      s.started = true;
+    } catch (...) {
+      s.err = std::current_exception();
+    }
+    s.send_ms = ms_since(t0) - s.send_start_ms;
+    std::lock_guard<std::mutex> lk(m);
+    --sends_pending;
+    cv.notify_all();
+    return true;
+  }
+
+  void wait_sends() {
+    std::unique_lock<std::mutex> lk(m);
+    cv.wait(lk, [this] { return sends_pending == 0; });
+  }
+};
+
+struct ShardedResult {
+  bool merged = false;
+  std::vector<std::pair<std::string, at::Tensor>> outs;  // merged == true
+  std::vector<GrpcChannel::ParsedResult> parts;          // merged == false
+};
+
+// Runs WITHOUT the GIL. `contig` (kept alive by the caller for the whole
+// call) backs every region pointer in `inputs`.
+ShardedResult run_predict_sharded(
+    const std::vector<GrpcChannel*>& channels, const std::string& path,
+    const std::string& model_name, int64_t version,
+    const std::string& signature, const std::vector<std::string>& names,
+    const std::vector<tfsshard::Input>& inputs,
+    const std::vector<int>& input_devices, int shards, int parse_device,
+    double timeout) {
+  static const char* trace_path = std::getenv("MI355X_SHARDED_TRACE");
+  const auto t0 = std::chrono::steady_clock::now();
+  const size_t n = size_t(shards);
+  auto call = std::make_shared<ShardedCall>(n);
+  call->path = path;
+  call->timeout = timeout;
+  call->parse_device = parse_device;
+  call->t0 = t0;
+
+  // plan: per-shard skeleton + regions, and the request's channels
+  const auto sizes = tfsshard::shard_sizes(inputs[0].shape[0], shards);
+  const uint32_t n_ch = uint32_t(channels.size());
+  const uint32_t start =
+      tfsshard::next_start_channel(g_shard_rotation, n_ch, uint32_t(shards));
+  int64_t row = 0;
+  for (size_t i = 0; i < n; ++i) {
+    auto& s = call->shards[i];
+    s.plan = tfsshard::plan_shard(model_name, version, signature, names,
+                                  inputs, row, sizes[i]);
+    row += sizes[i];
+    s.regions.reserve(s.plan.regions.size());
+    for (const auto& r : s.plan.regions)
+      s.regions.push_back(WireRegion{r.offset, r.nbytes, r.ptr, r.device});
+    s.ch = channels[tfsshard::shard_channel(start, uint32_t(i), n_ch)];
+  }
+  const double plan_ms = ms_since(t0);
+
+  // producer ordering: the staging DMA must see everything the CALLER's
+  // current stream has queued on the inputs — one host sync per input
+  // device per request, on the caller's own thread
+  for (int dev : input_devices) {
+    hipStream_t cur = c10::hip::getCurrentHIPStream(
+                          static_cast<c10::DeviceIndex>(dev))
+                          .stream();
+    if (hipStreamSynchronize(cur) != hipSuccess)
+      throw RpcCallError(GRPC_INTERNAL,
+                         "producer stream synchronize failed");
+  }
+  const double sync_ms = ms_since(t0) - plan_ms;
+
+  // sends: shard 0 here, the rest offered to the pool (and reclaimed by
+  // this thread if the pool has not picked them up by then)
+  for (size_t i = 1; i < n; ++i)
+    (void)SenderPool::instance().submit([call, i] { call->try_send(i); });
+  for (size_t i = 0; i < n; ++i) call->try_send(i);
+  call->wait_sends();
+  const double sends_done_ms = ms_since(t0);
+
+  // completion: EVERY started stream is waited on (wait/wait_parsed RST
+  // the stream and quiesce its copy stream on deadline) before the first
+  // error is rethrown
+  ShardedResult res;
+  res.parts.resize(n);
+  std::exception_ptr first_err;
+  for (size_t i = 0; i < n; ++i) {
+    auto& s = call->shards[i];
+    if (!s.started) {
+      if (!first_err) first_err = s.err;
+      continue;
+    }
+    double remaining = 0.0;
+    if (timeout > 0) {
+      remaining = timeout - ms_since(t0) * 1e-3;
+      if (remaining < 1e-3) remaining = 1e-3;
+    }
+    try {
+      if (parse_device >= 0) {
+        res.parts[i] = s.ch->wait_parsed(s.id, remaining);
+      } else {
+        res.parts[i].resp = s.ch->wait(s.id, remaining);
+      }
+    } catch (...) {
+      if (!first_err) first_err = std::current_exception();
+    }
+  }
+  const double wait_ms = ms_since(t0) - sends_done_ms;
+  if (first_err) {
+    res.parts.clear();
+    try {
+      std::rethrow_exception(first_err);
+    } catch (const RpcCallError&) {
+      throw;
+    } catch (const std::exception& e) {
+      throw RpcCallError(GRPC_INTERNAL, e.what());
+    }
+  }
+
+  // merge: only when every shard was device-parsed with the same outputs
+  const auto t_merge = std::chrono::steady_clock::now();
+  bool all_parsed = parse_device >= 0;
+  for (auto& p : res.parts) all_parsed = all_parsed && p.parsed_ok;
+  if (all_parsed) {
+    const auto& first = res.parts[0].outs;
+    for (auto& p : res.parts) {
+      all_parsed = all_parsed && p.outs.size() == first.size();
+      for (size_t k = 0; all_parsed && k < first.size(); ++k)
+        all_parsed = p.outs[k].first == first[k].first;
+    }
+  }
+  if (all_parsed) {
+    const auto& first = res.parts[0].outs;
+    for (size_t k = 0; k < first.size(); ++k) {
+      if (first[k].second.dim() == 0) {
+        res.outs.emplace_back(first[k].first, first[k].second);
+        continue;
+      }
+      std::vector<at::Tensor> pieces;
+      pieces.reserve(n);
+      for (auto& p : res.parts) pieces.push_back(p.outs[k].second);
+      // on the caller's current stream; wait_parsed recorded that stream
+      // on every piece, so the allocator orders their reuse after the cat
+      res.outs.emplace_back(first[k].first, at::cat(pieces, 0));
+    }
+    res.merged = true;
+    res.parts.clear();
+  }
+
+  if (trace_path) {
+    // one JSON line per request (diagnostic; same style as
+    // MI355X_STAGING_TRACE)
+    std::string line = "{\"shards\": " + std::to_string(n) +
+                       ", \"start_channel\": " + std::to_string(start) +
+                       ", \"plan_ms\": " + std::to_string(plan_ms) +
+                       ", \"sync_ms\": " + std::to_string(sync_ms) +
+                       ", \"send_start_ms\": [";
+    for (size_t i = 0; i < n; ++i)
+      line += (i ? "," : "") + std::to_string(call->shards[i].send_start_ms);
+    line += "], \"send_ms\": [";
+    for (size_t i = 0; i < n; ++i)
+      line += (i ? "," : "") + std::to_string(call->shards[i].send_ms);
+    line += "], \"sends_done_ms\": " + std::to_string(sends_done_ms) +
+            ", \"wait_ms\": " + std::to_string(wait_ms) +
+            ", \"merge_ms\": " + std::to_string(ms_since(t_merge)) +
+            ", \"merged\": " + (res.merged ? "true" : "false") +
+            ", \"total_ms\": " + std::to_string(ms_since(t0)) + "}\n";
+    FILE* f = std::fopen(trace_path, "a");
+    if (f) {
+      std::fputs(line.c_str(), f);
+      std::fclose(f);
+    }
+  }
+  return res;
+}
 
 }  // namespace
 
@@ -2205,6 +2534,96 @@ class NativeRpcError(Exception):
             return OwnedBuf(std::move(resp));
           },
           py::arg("id"), py::arg("timeout") = 0.0)
+      .def_property_readonly(
+          "streams_started", &GrpcChannel::streams_started,
+          "Number of streams (calls) opened on this channel so far.")
       .def("close", &GrpcChannel::close,
            py::call_guard<py::gil_scoped_release>());
+
+  m.def(
+      "predict_sharded",
+      [](const std::vector<GrpcChannel*>& channels, const std::string& path,
+         const std::string& model_name, int64_t version,
+         const std::string& signature,
+         const std::vector<std::string>& names,
+         const std::vector<at::Tensor>& tensors, int shards,
+         int parse_device, double timeout) -> py::object {
+        // with the GIL: validate, make contiguous; `contig` keeps every
+        // payload alive in C++ until the last send has returned
+        if (channels.empty()) throw py::value_error("no channels");
+        for (auto* ch : channels)
+          if (ch == nullptr) throw py::value_error("channel is None");
+        if (names.size() != tensors.size() || tensors.empty())
+          throw py::value_error("names/tensors mismatch");
+        if (shards < 1) throw py::value_error("shards must be >= 1");
+        std::vector<at::Tensor> contig(tensors.size());
+        std::vector<tfsshard::Input> inputs(tensors.size());
+        std::vector<int> input_devices;
+        for (size_t i = 0; i < tensors.size(); ++i) {
+          const at::Tensor& t = tensors[i];
+          if (t.dim() == 0)
+            throw py::value_error("sharded inputs need a batch dimension");
+          if (!t.is_cuda() && !t.is_cpu())
+            throw py::value_error("inputs must be CPU or GPU tensors");
+          if (t.size(0) != tensors[0].size(0))
+            throw py::value_error("inputs disagree on the dim-0 size");
+          contig[i] = t.contiguous();
+          auto& in = inputs[i];
+          in.dtype = scalar_to_tf_dtype(contig[i].scalar_type());
+          auto sz = contig[i].sizes();
+          in.shape.assign(sz.begin(), sz.end());
+          in.elem_size = size_t(contig[i].element_size());
+          in.data = static_cast<const uint8_t*>(contig[i].const_data_ptr());
+          in.device = contig[i].is_cuda();
+          if (in.device) {
+            int dev = int(contig[i].get_device());
+            if (std::find(input_devices.begin(), input_devices.end(), dev) ==
+                input_devices.end())
+              input_devices.push_back(dev);
+          }
+        }
+        if (tensors[0].size(0) < shards)
+          throw py::value_error("batch is smaller than the shard count");
+        ShardedResult r;
+        {
+          py::gil_scoped_release release;
+          r = run_predict_sharded(channels, path, model_name, version,
+                                  signature, names, inputs, input_devices,
+                                  shards, parse_device, timeout);
+        }
+        if (r.merged) {
+          py::dict d;
+          for (auto& kv : r.outs) d[py::str(kv.first)] = kv.second;
+          return std::move(d);
+        }
+        py::list parts;
+        for (auto& p : r.parts) {
+          py::object outs = py::none();
+          if (p.parsed_ok) {
+            py::dict d;
+            for (auto& kv : p.outs) d[py::str(kv.first)] = kv.second;
+            outs = std::move(d);
+          }
+          parts.append(py::make_tuple(outs, OwnedBuf(std::move(p.resp))));
+        }
+        return std::move(parts);
+      },
+      py::arg("channels"), py::arg("path"), py::arg("model_name"),
+      py::arg("version"), py::arg("signature"), py::arg("names"),
+      py::arg("tensors"), py::arg("shards"), py::arg("parse_device") = -1,
+      py::arg("timeout") = 0.0,
+      "One logical Predict split along dim 0 into `shards` PredictRequests "
+      "sent in parallel over distinct channels (rotating between "
+      "requests), behind a single GIL release. Returns the merged "
+      "{name: device tensor} dict when every shard was device-parsed, "
+      "else the per-shard [(outs | None, raw buf), ...] list.");
+
+  m.def(
+      "shutdown_sender_pool", [] { SenderPool::instance().shutdown(); },
+      py::call_guard<py::gil_scoped_release>(),
+      "Drain and join the sharded-send thread pool (restarted lazily by "
+      "the next sharded call).");
+  m.attr("SENDER_POOL_SIZE") = tfsshard::kSenderPoolSize;
+  py::module_::import("atexit").attr("register")(
+      m.attr("shutdown_sender_pool"));
 }

@@ -17,6 +17,7 @@
 #include <thread>
 #include <vector>
 
+#include "sharded.h"
 #include "wire.h"
 
 namespace py = pybind11;
@@ -151,9 +152,10 @@ py::bytes serialize_predict(bool is_request, const std::string& model_name,
 //   regions  = [(offset, nbytes, ptr, is_device), ...] ascending offsets;
 //   keepalive = the contiguous tensors backing `ptr` — the caller must
 //   hold it until the send completes.
-// Host spans smaller than kStreamMinSpan are copied into the skeleton
-// (fewer iovec regions beats the copy at that size).
-constexpr size_t kStreamMinSpan = 64 * 1024;
+// Host spans smaller than kStreamMinSpan (sharded.h, shared with the
+// transport's sharded planner) are copied into the skeleton (fewer iovec
+// regions beats the copy at that size).
+using tfsshard::kStreamMinSpan;
 
 py::tuple serialize_predict_streaming(bool is_request,
                                       const std::string& model_name,

@@ -68,6 +68,9 @@ struct Ctx {
   void* buf[2] = {nullptr, nullptr};
   hipEvent_t evt[2] = {};
   hipEvent_t producer_evt = {};
+  // time the current lease blocked in Pool::acquire() (trace runs only;
+  // reported as acquire_ms on this lease's d2h trace lines)
+  double acquire_ms = 0.0;
 
   void init() {
     MI355X_STAGING_CHECK(
@@ -145,8 +148,9 @@ struct Ctx {
       // line writes (trace is a diagnostic, not a hot-path feature)
       FILE* f = std::fopen(trace_path, "a");
       if (f) {
-        std::fprintf(f, "{\"nbytes\": %zu, \"chunks\": %zu, \"wait_ms\": [",
-                     nbytes, nchunks);
+        std::fprintf(f, "{\"nbytes\": %zu, \"chunks\": %zu, "
+                     "\"acquire_ms\": %.4f, \"wait_ms\": [",
+                     nbytes, nchunks, acquire_ms);
         for (size_t i = 0; i < wait_ms.size(); ++i)
           std::fprintf(f, "%s%.4f", i ? "," : "", wait_ms[i]);
         std::fprintf(f, "], \"consume_ms\": [");
@@ -226,7 +230,17 @@ class Pool {
 // RAII lease over a pooled context.
 struct Lease {
   Ctx* ctx;
-  Lease() : ctx(Pool::instance().acquire()) {}
+  Lease() {
+    if (std::getenv("MI355X_STAGING_TRACE") == nullptr) {
+      ctx = Pool::instance().acquire();
+      return;
+    }
+    auto t0 = std::chrono::steady_clock::now();
+    ctx = Pool::instance().acquire();
+    ctx->acquire_ms = std::chrono::duration<double, std::milli>(
+                          std::chrono::steady_clock::now() - t0)
+                          .count();
+  }
   ~Lease() { Pool::instance().release(ctx); }
   Lease(const Lease&) = delete;
   Lease& operator=(const Lease&) = delete;

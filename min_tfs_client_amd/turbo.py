@@ -302,6 +302,11 @@ class TurboPredictClient:
         if self.__send_pool is not None:
             self.__send_pool.shutdown(wait=False)
             self.__send_pool = None
+        if self.backend == "native":
+            from . import _transport
+            # drains and joins the C++ sharded-send pool (GIL released;
+            # restarted lazily if another client is still sending)
+            _transport.shutdown_sender_pool()
         for ch in self._channels:
             ch.close()
 
@@ -484,6 +489,12 @@ class TurboPredictClient:
         must share its dim-0 size; uneven tails are handled. Falls back to
         plain predict when sharding is not applicable. Wire-compatible:
         the server just sees `shards` ordinary PredictRequests.
+
+        On the native backend with streaming on, the whole request is one
+        C++ call (``_transport.predict_sharded``): a request's shards ride
+        distinct channels and the first channel rotates between requests.
+        ``MI355X_NATIVE_SHARDED=0`` keeps the per-shard python
+        orchestration (same bytes on the wire) for A/B runs.
         """
         if shards <= 1 or len(self._stubs) < 2:
             return self.predict(model_name, inputs, timeout, model_version,
@@ -507,18 +518,28 @@ class TurboPredictClient:
         if use_streaming and self.backend != "native":
             raise ValueError("streaming=True requires backend='native'")
 
+        dev = str(output_device) if output_device is not None else "cpu"
+        parse_dev = -1
+        if (use_streaming and dev.startswith("cuda") and torch is not None
+                and os.environ.get("MI355X_RX_PARSE", "1") != "0"):
+            parse_dev = torch.device(dev).index or 0
+
+        if (use_streaming and torch is not None
+                and os.environ.get("MI355X_NATIVE_SHARDED", "1") != "0"):
+            # one native call per request: plan, producer sync, parallel
+            # sends over rotating channels, waits and the device concat
+            # all run behind a single GIL release
+            # (ops/csrc/grpc_transport.cpp predict_sharded)
+            return self._predict_sharded_native(
+                model_name, keys, inputs, shards, timeout, model_version,
+                signature_name, dev, parse_dev, copy_mode)
+
         shard_views = []
         off = 0
         for n in sizes:
             shard_views.append({k: inputs[k].narrow(0, off, n)
                                 for k in keys})
             off += n
-
-        dev = str(output_device) if output_device is not None else "cpu"
-        parse_dev = -1
-        if (use_streaming and dev.startswith("cuda") and torch is not None
-                and os.environ.get("MI355X_RX_PARSE", "1") != "0"):
-            parse_dev = torch.device(dev).index or 0
 
         def send_shard(i):
             # serialize + send one shard. On the native backend the send
@@ -565,6 +586,35 @@ class TurboPredictClient:
             for fut in futs:
                 fut.cancel()
             raise
+        merged = {}
+        for k in parts[0]:
+            vals = [p[k] for p in parts]
+            if isinstance(vals[0], torch.Tensor) and vals[0].dim() > 0:
+                merged[k] = torch.cat(vals, dim=0)
+            else:
+                merged[k] = vals[0]
+        return merged
+
+    @_translate_native_error
+    def _predict_sharded_native(self, model_name, keys, inputs, shards,
+                                timeout, model_version, signature_name,
+                                dev, parse_dev, copy_mode):
+        from . import _transport
+        with trace_span("turbo.sharded_native", model=model_name,
+                        shards=shards):
+            res = _transport.predict_sharded(
+                self._channels, _PREDICT_PATH, model_name,
+                -1 if model_version is None else model_version,
+                signature_name, keys, [inputs[k] for k in keys], shards,
+                parse_dev, timeout or 0.0)
+        if isinstance(res, dict):  # every shard device-parsed and merged
+            return res
+        parts = []
+        for outs, raw in res:
+            if outs is None:
+                _s, outs, _ = self._native.parse_predict_response(
+                    raw, dev, copy_mode)
+            parts.append(outs)
         merged = {}
         for k in parts[0]:
             vals = [p[k] for p in parts]

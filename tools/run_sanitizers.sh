@@ -13,3 +13,7 @@ g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer \
     tests/cpp/h2_test.cpp -o build/sanitize/h2_test_asan -lpthread
 ./build/sanitize/h2_test_asan
 echo "ASAN+UBSAN h2/hpack test passed"
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer \
+    tests/cpp/sharded_test.cpp -o build/sanitize/sharded_test_asan
+./build/sanitize/sharded_test_asan
+echo "ASAN+UBSAN sharded planner test passed"
