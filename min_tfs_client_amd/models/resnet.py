@@ -84,13 +84,18 @@ def resnet50_servable(device: str = "cpu", dtype=torch.float32,
     ``input_format="uint8_nhwc"``: "images" is DT_UINT8 (N,224,224,3) raw
     pixels — a quarter of the wire and H2D bytes; the server applies the
     ImageNet normalization and NHWC->NCHW in one fused kernel
-    (``preprocess.ImagePreprocess``) before the model."""
+    (``preprocess.ImagePreprocess``) before the model.
+    ``input_format="uint8_nhwc_resize"``: "images" is DT_UINT8 (N,H,W,3) raw
+    pixels of any size; the same kernel pass also resizes the shorter side
+    to 256 (bilinear, aspect ratio kept) and takes the 224x224 centre crop
+    (``ImagePreprocess(resize=256, center_crop=224)``). All images of one
+    request share one size."""
     from ..server import Servable
 
-    if input_format not in ("float_nchw", "uint8_nhwc"):
+    if input_format not in ("float_nchw", "uint8_nhwc", "uint8_nhwc_resize"):
         raise ValueError(
-            f"input_format must be 'float_nchw' or 'uint8_nhwc', got "
-            f"{input_format!r}")
+            f"input_format must be 'float_nchw', 'uint8_nhwc' or "
+            f"'uint8_nhwc_resize', got {input_format!r}")
 
     torch.manual_seed(seed)
     model = resnet50().to(device=device, dtype=dtype).eval()
@@ -110,6 +115,11 @@ def resnet50_servable(device: str = "cpu", dtype=torch.float32,
         preprocess = {"images": ImagePreprocess(
             IMAGENET_MEAN, IMAGENET_STD, out_dtype=dtype, layout="nchw",
             device=device)}
+    elif input_format == "uint8_nhwc_resize":
+        images_sig = (4, [-1, -1, -1, 3])                   # DT_UINT8
+        preprocess = {"images": ImagePreprocess(
+            IMAGENET_MEAN, IMAGENET_STD, out_dtype=dtype, layout="nchw",
+            device=device, resize=256, center_crop=224)}
     else:
         images_sig = (1, [-1, 3, 224, 224])                 # DT_FLOAT
         preprocess = None

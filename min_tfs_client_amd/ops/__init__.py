@@ -159,6 +159,129 @@ def image_u8_to_float(tensor, mean, std, out_dtype=None, layout="nchw",
     return y.to(out_dtype).contiguous()
 
 
+RESIZE_MAX_SIDE = 16384
+
+
+def _resize_taps(n_out, offset, ratio, n_in):
+    """Source indices and weights of ``n_out`` output coordinates starting
+    at ``offset`` of the resized axis: fp32 tensor ops, one rounding each."""
+    o = torch.arange(offset, offset + n_out, dtype=torch.float32)
+    s = (((o + 0.5) * ratio) - 0.5).clamp(min=0.0)
+    i0 = s.floor().to(torch.int64).clamp(max=n_in - 1)
+    i1 = (i0 + 1).clamp(max=n_in - 1)
+    return i0, i1, s - i0.float()
+
+
+def image_u8_resize_to_float(tensor, size, mean, std, crop=None,
+                             out_dtype=None, layout="nchw",
+                             pixel_scale=1.0 / 255.0, _variant=0):
+    """Fused uint8 image ingest with bilinear resize and crop: a contiguous
+    ``[N,Hin,Win,C]`` uint8 tensor, ``C`` in 1..4, is resized to a virtual
+    ``size=(Hr,Wr)`` image, the window ``crop=(top,left,Hc,Wc)`` of that image
+    (``None``: all of it) is normalized as in :func:`image_u8_to_float` and
+    returned as ``[N,C,Hc,Wc]`` (``layout="nhwc"``: ``[N,Hc,Wc,C]``).
+
+    Half-pixel-centre bilinear without antialiasing, the family of
+    ``F.interpolate(mode="bilinear", align_corners=False, antialias=False)``,
+    pinned to these fp32 operations (each rounded once, none fused)::
+
+        rw = float32(Win / Wr)    rh = float32(Hin / Hr)
+        sx = max(((float(ox + left) + 0.5) * rw) - 0.5, 0)
+        x0 = min(int(floor(sx)), Win-1)   x1 = min(x0+1, Win-1)
+        wx = sx - float(x0)                  # rows likewise: top, rh, Hin
+        t  = p[y0,x0] + wx * (p[y0,x1] - p[y0,x0])
+        b  = p[y1,x0] + wx * (p[y1,x1] - p[y1,x0])
+        v  = t + wy * (b - t)
+        y  = out_dtype((v * scale_c) + bias_c)
+
+    With ``size == (Hin,Win)`` the weights are exactly 0 and the result is
+    bit-identical to :func:`image_u8_to_float`; a cropped call equals the
+    same window sliced out of the uncropped call, bit for bit. Against
+    ``F.interpolate`` the result differs by rounding only.
+
+    Device tensors run the gfx950 kernel (one pass, no eager fallback); CPU
+    tensors use an eager expression of exactly these operations, so both are
+    bit-identical and CPU-only servers work too. All sides (``Hin``, ``Win``,
+    ``Hr``, ``Wr``) must be in 1..16384. Invalid arguments raise
+    ``ValueError`` on both paths; ``N == 0`` returns an empty tensor."""
+    import numpy as np
+
+    name = "image_u8_resize_to_float"
+    if out_dtype is None:
+        out_dtype = torch.float32
+    if layout not in ("nchw", "nhwc"):
+        raise ValueError(f"layout must be 'nchw' or 'nhwc', got {layout!r}")
+    if out_dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError(
+            f"out_dtype must be float32, bfloat16 or float16, got {out_dtype}")
+    if not isinstance(tensor, torch.Tensor):
+        raise ValueError(f"{name} expects a torch tensor")
+    if tensor.dtype != torch.uint8:
+        raise ValueError(f"{name} expects uint8 pixels, got {tensor.dtype}")
+    if tensor.dim() != 4:
+        raise ValueError(
+            f"{name} expects [N,H,W,C], got rank {tensor.dim()}")
+    if not tensor.is_contiguous():
+        raise ValueError(f"{name} expects a contiguous tensor")
+    N, Hin, Win, C = (int(d) for d in tensor.shape)
+    if not 1 <= C <= 4:
+        raise ValueError(f"{name} supports 1..4 channels, got {C}")
+    if len(mean) != C or len(std) != C:
+        raise ValueError(
+            f"mean/std need {C} entries (one per channel), got "
+            f"{len(mean)}/{len(std)}")
+    try:
+        Hr, Wr = (int(d) for d in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"size must be (H, W), got {size!r}") from None
+    for label, v in (("input height", Hin), ("input width", Win),
+                     ("resized height", Hr), ("resized width", Wr)):
+        if not 1 <= v <= RESIZE_MAX_SIDE:
+            raise ValueError(
+                f"{name}: {label} must be in 1..{RESIZE_MAX_SIDE}, got {v}")
+    if crop is None:
+        top, left, Hc, Wc = 0, 0, Hr, Wr
+    else:
+        try:
+            top, left, Hc, Wc = (int(d) for d in crop)
+        except (TypeError, ValueError):
+            raise ValueError(
+                f"crop must be (top, left, height, width), got {crop!r}"
+            ) from None
+        if Hc < 1 or Wc < 1:
+            raise ValueError(f"crop extent must be positive, got {Hc}x{Wc}")
+        if top < 0 or left < 0 or top + Hc > Hr or left + Wc > Wr:
+            raise ValueError(
+                f"crop window (top={top}, left={left}, {Hc}x{Wc}) is not "
+                f"inside the resized image {Hr}x{Wr}")
+    scale, bias = normalization_constants(mean, std, pixel_scale)
+    rh = float(np.float32(Hin / Hr))
+    rw = float(np.float32(Win / Wr))
+    if tensor.is_cuda:
+        return require_native().u8_nhwc_resize_normalize(
+            tensor, rh, rw, top, left, Hc, Wc, scale, bias, out_dtype,
+            layout == "nchw", int(_variant))
+    if N == 0:
+        shape = (0, C, Hc, Wc) if layout == "nchw" else (0, Hc, Wc, C)
+        return torch.empty(shape, dtype=out_dtype)
+    y0, y1, wy = _resize_taps(Hc, top, rh, Hin)
+    x0, x1, wx = _resize_taps(Wc, left, rw, Win)
+    p = tensor.float()
+    wx = wx.view(1, 1, Wc, 1)
+    wy = wy.view(1, Hc, 1, 1)
+    r0, r1 = p[:, y0], p[:, y1]
+    p00, p10 = r0[:, :, x0], r1[:, :, x0]
+    t = p00 + wx * (r0[:, :, x1] - p00)
+    b = p10 + wx * (r1[:, :, x1] - p10)
+    v = t + wy * (b - t)
+    s = torch.tensor(scale, dtype=torch.float32)
+    bs = torch.tensor(bias, dtype=torch.float32)
+    y = (v * s.view(1, 1, 1, C)) + bs.view(1, 1, 1, C)
+    if layout == "nchw":
+        y = y.permute(0, 3, 1, 2)
+    return y.to(out_dtype).contiguous()
+
+
 def masked_mean_pool(hidden, mask=None, normalize=False):
     """Fused masked mean-pool head: ``[B,S,H]`` hidden state (f32, bf16 or
     f16, contiguous) -> fp32 ``[B,H]``, one vector per sequence.

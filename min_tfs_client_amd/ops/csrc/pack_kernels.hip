@@ -11,6 +11,8 @@
 //  * affine int8 quantize/dequantize (the "cast/quantize" pack stage),
 //  * fused uint8 image ingest: dequantize + per-channel normalize + NCHW
 //    (server-side preprocessing, so clients ship 1 byte per pixel value),
+//  * the same ingest with a bilinear resize + crop fused in (images of any
+//    size, source taps staged through LDS),
 //  * fused masked mean-pool (+ L2 normalize) head: [B,S,H] hidden state ->
 //    fp32 [B,H] sentence embeddings, so responses ship S x fewer bytes,
 // plus the host-side staging machinery: pinned double-buffered
@@ -27,6 +29,8 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <mutex>
@@ -510,6 +514,225 @@ __global__ void u8_nhwc_normalize_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// fused uint8 image ingest with bilinear resize + crop
+// ---------------------------------------------------------------------------
+// uint8 NHWC [N,Hin,Win,C] -> [N,C,Hc,Wc] (or [N,Hc,Wc,C]): half-pixel-centre
+// bilinear resize to a virtual (Hr,Wr) image, a crop window of it, then the
+// same normalize + cast as u8_nhwc_normalize_kernel. Every step is one IEEE
+// fp32 operation, nothing contracted (ox is the output column, rw =
+// float(Win/Wr) rounded once on the host; rows likewise with top, rh, Hin):
+//
+//   sx = max(fsub(fmul(fadd(float(ox + left), 0.5), rw), 0.5), 0)
+//   x0 = min(int(floor(sx)), Win-1)   x1 = min(x0+1, Win-1)
+//   wx = fsub(sx, float(x0))
+//   t  = p[y0,x0] + wx * (p[y0,x1] - p[y0,x0])      b likewise on row y1
+//   v  = t + wy * (b - t)
+//   y  = Out(fadd(fmul(v, scale_c), bias_c))
+//
+// With (Hr,Wr) == (Hin,Win) the weights are exactly 0 and the result is
+// bit-identical to u8_nhwc_normalize_kernel.
+//
+// Shape of the kernel. A 256-thread workgroup owns a tile of the output:
+// 2^twl_log2 lane runs wide and 256 >> twl_log2 rows high; a lane owns a run
+// of kResizePx = 8 consecutive output columns of one output row and writes
+// them with 16 B stores, one vector run per channel plane (NCHW) or one
+// contiguous run (NHWC). A work item is (image, row tile, column tile);
+// workgroups grid-stride over work items under the usual grid cap.
+//
+// Source taps, two paths, chosen per work item (uniform in the workgroup):
+//  * LDS path: every output row of the tile needs source rows y0 and y1 over
+//    the same contiguous column span [x0(first column), x1(last column)].
+//    The workgroup copies those 2 * rows spans into LDS with 16 B-aligned
+//    16 B global loads (each span keeps its own misalignment `shift`, so the
+//    loads are aligned whatever the row base is; a 16 B chunk that is not
+//    wholly inside the tensor is read bytewise, in bounds) and the lanes
+//    gather their taps from LDS.
+//  * direct path: taps are byte loads from global memory. Taken when the
+//    host found that the tile's spans exceed kResizeLdsBytes (span_stride ==
+//    0: large downscale ratios), or when a tile's span does not fit the span
+//    stride the host estimated.
+// Stores go scalar for a run that crosses the row end and when the
+// destination, or for NCHW the plane stride, is not 16 B-aligned.
+constexpr int kResizeBlock = 256;
+constexpr int kResizePx = 8;             // output columns per lane
+constexpr int kResizeLdsBytes = 32768;
+constexpr int kResizeMinTwlLog2 = 3;     // tile: 8 runs x 32 rows ...
+constexpr int kResizeMaxTwlLog2 = 5;     // ... to 32 runs (256 columns) x 8
+
+struct U8ResizeParams {
+  float scale[4];
+  float bias[4];
+  float rh, rw;
+  int Hin, Win, Hc, Wc, top, left;
+  int twl_log2;      // lane runs per tile row, log2
+  int tiles_x, tiles_y;
+  int span_stride;   // LDS bytes per source-row span (multiple of 16), 0: direct
+};
+
+// Source index and weight of one output coordinate.
+__device__ __forceinline__ void resize_tap(int o, int offset, float ratio,
+                                           int n_in, int& i0, int& i1,
+                                           float& w) {
+  const float s = fmaxf(
+      __fsub_rn(__fmul_rn(__fadd_rn(float(o + offset), 0.5f), ratio), 0.5f),
+      0.f);
+  i0 = min(int(floorf(s)), n_in - 1);
+  i1 = min(i0 + 1, n_in - 1);
+  w = __fsub_rn(s, float(i0));
+}
+
+// One lane's run: kResizePx output columns from ox0 of one output row. r0/r1
+// point at column `xb` of source rows y0/y1: global memory with xb = 0, or
+// the LDS image of the tile's span with xb = its first column.
+template <typename CVT, int C, bool NCHW, typename Ptr>
+__device__ __forceinline__ void resize_run(
+    Ptr r0, Ptr r1, int xb, float wy, int ox0,
+    typename CVT::Out* __restrict__ dst, int64_t plane,
+    const U8ResizeParams& p) {
+  using Out = typename CVT::Out;
+  constexpr int PERV = 16 / int(sizeof(Out));
+  Out vout[C * kResizePx];   // NCHW: [c][k], NHWC: [k][c]
+#pragma unroll
+  for (int k = 0; k < kResizePx; ++k) {
+    // a run that crosses the row end computes its last column again; the
+    // duplicates are never stored
+    const int ox = min(ox0 + k, p.Wc - 1);
+    int x0, x1;
+    float wx;
+    resize_tap(ox, p.left, p.rw, p.Win, x0, x1, wx);
+    const int b0 = (x0 - xb) * C, b1 = (x1 - xb) * C;   // both >= 0
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const float p00 = float(r0[b0 + c]);
+      const float p01 = float(r0[b1 + c]);
+      const float p10 = float(r1[b0 + c]);
+      const float p11 = float(r1[b1 + c]);
+      const float t = __fadd_rn(p00, __fmul_rn(wx, __fsub_rn(p01, p00)));
+      const float b = __fadd_rn(p10, __fmul_rn(wx, __fsub_rn(p11, p10)));
+      const float v = __fadd_rn(t, __fmul_rn(wy, __fsub_rn(b, t)));
+      vout[NCHW ? c * kResizePx + k : k * C + c] =
+          CVT::cvt(__fadd_rn(__fmul_rn(v, p.scale[c]), p.bias[c]));
+    }
+  }
+  const bool vec = ox0 + kResizePx <= p.Wc &&
+                   (reinterpret_cast<uintptr_t>(dst) & 15) == 0 &&
+                   (!NCHW || (plane * int64_t(sizeof(Out))) % 16 == 0);
+  if (vec) {
+    if constexpr (NCHW) {
+#pragma unroll
+      for (int c = 0; c < C; ++c)
+#pragma unroll
+        for (int v = 0; v < kResizePx / PERV; ++v)
+          reinterpret_cast<int4*>(dst + c * plane)[v] =
+              *reinterpret_cast<const int4*>(vout + c * kResizePx + v * PERV);
+    } else {
+#pragma unroll
+      for (int v = 0; v < C * kResizePx / PERV; ++v)
+        reinterpret_cast<int4*>(dst)[v] =
+            *reinterpret_cast<const int4*>(vout + v * PERV);
+    }
+  } else {
+    const int span = min(kResizePx, p.Wc - ox0);
+#pragma unroll
+    for (int k = 0; k < kResizePx; ++k) {
+      if (k < span) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+          if constexpr (NCHW) dst[c * plane + k] = vout[c * kResizePx + k];
+          else dst[k * C + c] = vout[k * C + c];
+        }
+      }
+    }
+  }
+}
+
+template <typename CVT, int C, bool NCHW>
+__global__ void __launch_bounds__(kResizeBlock) u8_nhwc_resize_normalize_kernel(
+    const uint8_t* __restrict__ in, typename CVT::Out* __restrict__ out,
+    int64_t N, U8ResizeParams p) {
+  using Out = typename CVT::Out;
+  __shared__ __attribute__((aligned(16))) uint8_t lds[kResizeLdsBytes];
+  static_assert(kResizePx % (16 / int(sizeof(Out))) == 0,
+                "a lane run must fill whole 16 B stores");
+  const int twl = 1 << p.twl_log2;               // lane runs per tile row
+  const int tr = kResizeBlock >> p.twl_log2;     // rows per tile
+  const int tw = twl * kResizePx;                // columns per tile
+  const int r = int(threadIdx.x) >> p.twl_log2;
+  const int j = int(threadIdx.x) & (twl - 1);
+  const int64_t plane = int64_t(p.Hc) * p.Wc;
+  const int64_t row_bytes = int64_t(p.Win) * C;
+  const uint8_t* const in_end = in + N * p.Hin * row_bytes;
+  const int64_t items = N * p.tiles_y * p.tiles_x;
+  for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+    const int tx = int(item % p.tiles_x);
+    const int ty = int((item / p.tiles_x) % p.tiles_y);
+    const int64_t n = item / (int64_t(p.tiles_x) * p.tiles_y);
+    const uint8_t* img = in + n * p.Hin * row_bytes;
+    const int oy = ty * tr + r;
+    const int ox0 = tx * tw + j * kResizePx;
+    const bool active = oy < p.Hc && ox0 < p.Wc;
+
+    // source column span of the tile, the same for every row of it
+    int xs_lo, xs_hi, unused;
+    float unused_w;
+    resize_tap(tx * tw, p.left, p.rw, p.Win, xs_lo, unused, unused_w);
+    resize_tap(min(tx * tw + tw, p.Wc) - 1, p.left, p.rw, p.Win, unused,
+               xs_hi, unused_w);
+    const int span_bytes = (xs_hi + 1 - xs_lo) * C;
+    // uniform in the workgroup: the barriers below are not divergent
+    const bool use_lds = p.span_stride > 0 && span_bytes + 15 <= p.span_stride;
+
+    int y0 = 0, y1 = 0;
+    float wy = 0.f;
+    if (active) resize_tap(oy, p.top, p.rh, p.Hin, y0, y1, wy);
+    Out* dst = NCHW
+        ? out + (n * C * p.Hc + oy) * p.Wc + ox0
+        : out + ((n * p.Hc + oy) * p.Wc + ox0) * C;
+
+    if (use_lds) {
+      const int nchunks = p.span_stride >> 4;
+      const int rows_here = min(tr, p.Hc - ty * tr);
+      const int total = 2 * rows_here * nchunks;
+      for (int idx = int(threadIdx.x); idx < total; idx += kResizeBlock) {
+        const int s = idx / nchunks;           // span: tile row s>>1, y(s&1)
+        const int k = idx - s * nchunks;
+        int sy0, sy1;
+        float sw;
+        resize_tap(ty * tr + (s >> 1), p.top, p.rh, p.Hin, sy0, sy1, sw);
+        const uint8_t* a0 =
+            img + ((s & 1) ? sy1 : sy0) * row_bytes + int64_t(xs_lo) * C;
+        const uint8_t* a_end = a0 + span_bytes;
+        const uint8_t* ca =
+            a0 - (reinterpret_cast<uintptr_t>(a0) & 15) + int64_t(k) * 16;
+        if (ca >= a_end) continue;
+        uint8_t* l = lds + s * p.span_stride + k * 16;
+        if (ca >= in && ca + 16 <= in_end) {
+          *reinterpret_cast<int4*>(l) = *reinterpret_cast<const int4*>(ca);
+        } else {
+          // the first or last chunk of the tensor: stay inside it
+          for (int b = 0; b < 16; ++b)
+            l[b] = (ca + b >= a0 && ca + b < a_end) ? ca[b] : uint8_t(0);
+        }
+      }
+      __syncthreads();
+      if (active) {
+        const uint8_t* g0 = img + y0 * row_bytes + int64_t(xs_lo) * C;
+        const uint8_t* g1 = img + y1 * row_bytes + int64_t(xs_lo) * C;
+        const int shift0 = int(reinterpret_cast<uintptr_t>(g0) & 15);
+        const int shift1 = int(reinterpret_cast<uintptr_t>(g1) & 15);
+        const uint8_t* l0 = lds + (2 * r) * p.span_stride + shift0;
+        const uint8_t* l1 = lds + (2 * r + 1) * p.span_stride + shift1;
+        resize_run<CVT, C, NCHW>(l0, l1, xs_lo, wy, ox0, dst, plane, p);
+      }
+      __syncthreads();   // lds is refilled by the next work item
+    } else if (active) {
+      resize_run<CVT, C, NCHW>(img + y0 * row_bytes, img + y1 * row_bytes, 0,
+                               wy, ox0, dst, plane, p);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // fused masked mean-pool head (+ optional L2 normalize): [B,S,H] -> [B,H]
 // ---------------------------------------------------------------------------
 // cnt_b  = #{s : mask[b,s] != 0}
@@ -959,6 +1182,112 @@ at::Tensor u8_nhwc_normalize(const at::Tensor& in, std::vector<double> scale,
         dim3(grid), dim3(block), 0, current_stream(), src,
         reinterpret_cast<typename CVT::Out*>(out.mutable_data_ptr()), HW, N,
         p);
+  };
+  auto by_layout = [&](auto cvt_tag, auto c_tag) {
+    if (out_nchw) launch(cvt_tag, c_tag, std::true_type{});
+    else launch(cvt_tag, c_tag, std::false_type{});
+  };
+  auto by_channels = [&](auto cvt_tag) {
+    switch (C) {
+      case 1: by_layout(cvt_tag, std::integral_constant<int, 1>{}); break;
+      case 2: by_layout(cvt_tag, std::integral_constant<int, 2>{}); break;
+      case 3: by_layout(cvt_tag, std::integral_constant<int, 3>{}); break;
+      default: by_layout(cvt_tag, std::integral_constant<int, 4>{});
+    }
+  };
+  if (out_dtype == at::kFloat) by_channels(IdF32{});
+  else if (out_dtype == at::kBFloat16) by_channels(F32ToBf16{});
+  else by_channels(F32ToF16{});
+  HIP_CHECK(hipGetLastError());
+  return out;
+}
+
+// Fused uint8 NHWC ingest with bilinear resize + crop; see the kernel section
+// for semantics and paths. `rh`/`rw` are float(Hin/Hr) and float(Win/Wr),
+// `scale`/`bias` as in u8_nhwc_normalize, all rounded to fp32 by the caller
+// (ops.image_u8_resize_to_float, which also validates the crop window
+// against the resized size). `variant` 0 picks the tap path per tile, 1
+// forces the direct path (for measurement).
+at::Tensor u8_nhwc_resize_normalize(
+    const at::Tensor& in, double rh, double rw, int64_t top, int64_t left,
+    int64_t Hc, int64_t Wc, std::vector<double> scale,
+    std::vector<double> bias, at::ScalarType out_dtype, bool out_nchw,
+    int64_t variant) {
+  TORCH_CHECK(in.is_cuda() && in.dim() == 4 && in.is_contiguous() &&
+              in.scalar_type() == at::kByte,
+              "u8_nhwc_resize_normalize expects a contiguous uint8 device "
+              "tensor [N,H,W,C]");
+  const int64_t N = in.size(0), Hin = in.size(1), Win = in.size(2),
+                C = in.size(3);
+  constexpr int64_t kMaxSide = 16384;
+  TORCH_CHECK(C >= 1 && C <= 4, "u8_nhwc_resize_normalize: C must be in 1..4");
+  TORCH_CHECK(Hin >= 1 && Hin <= kMaxSide && Win >= 1 && Win <= kMaxSide,
+              "u8_nhwc_resize_normalize: input sides must be in 1..16384");
+  TORCH_CHECK(Hc >= 1 && Wc >= 1 && top >= 0 && left >= 0 &&
+              top + Hc <= kMaxSide && left + Wc <= kMaxSide,
+              "u8_nhwc_resize_normalize: bad crop window");
+  TORCH_CHECK(rh > 0.0 && rw > 0.0,
+              "u8_nhwc_resize_normalize: ratios must be positive");
+  TORCH_CHECK(int64_t(scale.size()) == C && int64_t(bias.size()) == C,
+              "u8_nhwc_resize_normalize: scale/bias need one value per "
+              "channel");
+  TORCH_CHECK(out_dtype == at::kFloat || out_dtype == at::kBFloat16 ||
+              out_dtype == at::kHalf,
+              "u8_nhwc_resize_normalize: out_dtype must be f32, bf16 or f16");
+  auto out = out_nchw
+      ? at::empty({N, C, Hc, Wc}, in.options().dtype(out_dtype))
+      : at::empty({N, Hc, Wc, C}, in.options().dtype(out_dtype));
+  if (N == 0) return out;  // zero grid: never launch
+
+  U8ResizeParams p{};
+  for (int64_t c = 0; c < C; ++c) {
+    p.scale[c] = float(scale[c]);
+    p.bias[c] = float(bias[c]);
+  }
+  p.rh = float(rh);
+  p.rw = float(rw);
+  p.Hin = int(Hin); p.Win = int(Win);
+  p.Hc = int(Hc); p.Wc = int(Wc);
+  p.top = int(top); p.left = int(left);
+  // tile: the narrowest power-of-two count of lane runs that covers a row,
+  // within 8..32 runs (64..256 columns, 32..8 rows)
+  const int64_t runs = (Wc + kResizePx - 1) / kResizePx;
+  p.twl_log2 = kResizeMinTwlLog2;
+  while (p.twl_log2 < kResizeMaxTwlLog2 && (int64_t(1) << p.twl_log2) < runs)
+    ++p.twl_log2;
+  const int64_t tw = (int64_t(1) << p.twl_log2) * kResizePx;
+  const int64_t tr = kResizeBlock >> p.twl_log2;
+  p.tiles_x = int((Wc + tw - 1) / tw);
+  p.tiles_y = int((Hc + tr - 1) / tr);
+  // LDS bytes per source-row span: the widest span of a tile (an upper
+  // estimate; the kernel checks each tile's own span against it) plus up to
+  // 15 bytes of misalignment, in whole 16 B chunks
+  const int64_t span_px = std::min<int64_t>(
+      Win, int64_t(std::ceil(double(std::min(tw, Wc)) * double(p.rw))) + 3);
+  const int64_t span_stride = (span_px * C + 15 + 15) / 16 * 16;
+  p.span_stride =
+      (variant == 1 || 2 * tr * span_stride > kResizeLdsBytes)
+          ? 0 : int(span_stride);
+
+  // taps from LDS measured FASTER than the direct gather (variant 1) on
+  // MI355X, interleaved rounds in one process, u8 (N,256,341,3) -> NCHW,
+  // LDS vs direct:
+  //   224 centre crop  N=32  f32 10.8 vs 14.3 us, bf16 10.0 vs 17.2 us
+  //                    N=256 f32 47.8 vs 74.0 us, bf16 50.2 vs 99.2 us
+  //   2x downscale     N=32  bf16 8.7 vs 13.2 us
+  // At N=1 both sit on the launch floor (5.6-7.7 us, direct 0.6-0.9 us
+  // ahead with the crop). The LDS path ships wherever its spans fit.
+  const int64_t items = N * p.tiles_y * p.tiles_x;
+  const int grid = int(std::min<int64_t>(items, 2048));
+  const auto* src = static_cast<const uint8_t*>(in.const_data_ptr());
+
+  auto launch = [&](auto cvt_tag, auto c_tag, auto nchw_tag) {
+    using CVT = decltype(cvt_tag);
+    hipLaunchKernelGGL(
+        (u8_nhwc_resize_normalize_kernel<CVT, decltype(c_tag)::value,
+                                         decltype(nchw_tag)::value>),
+        dim3(grid), dim3(kResizeBlock), 0, current_stream(), src,
+        reinterpret_cast<typename CVT::Out*>(out.mutable_data_ptr()), N, p);
   };
   auto by_layout = [&](auto cvt_tag, auto c_tag) {
     if (out_nchw) launch(cvt_tag, c_tag, std::true_type{});

@@ -16,7 +16,8 @@ On-disk version-directory formats understood by the default loader:
   * ``model.json``          — {"family": "resnet50"|"bert_base",
                                "device": ..., "state_dict": "weights.pt"?}
                                plus optional I/O modes: "input_format"
-                               (resnet50), "output_format" and
+                               (resnet50: "float_nchw", "uint8_nhwc" or
+                               "uint8_nhwc_resize"), "output_format" and
                                "normalize_embedding" (bert_base)
   * ``model.pt``            — TorchScript module (torch.jit.load)
 plus TF-style ``assets.extra/tf_serving_warmup_requests`` (a TFRecord of
