@@ -76,7 +76,8 @@ def resnet50(num_classes: int = 1000) -> ResNet:
 
 
 def resnet50_servable(device: str = "cpu", dtype=torch.float32,
-                      seed: int = 0, input_format: str = "float_nchw"):
+                      seed: int = 0, input_format: str = "float_nchw",
+                      antialias: bool = False):
     """ResNet-50 Servable: input alias "images", output "logits" (N,1000).
 
     ``input_format="float_nchw"`` (default): "images" is DT_FLOAT
@@ -89,13 +90,20 @@ def resnet50_servable(device: str = "cpu", dtype=torch.float32,
     pixels of any size; the same kernel pass also resizes the shorter side
     to 256 (bilinear, aspect ratio kept) and takes the 224x224 centre crop
     (``ImagePreprocess(resize=256, center_crop=224)``). All images of one
-    request share one size."""
+    request share one size. ``antialias=True`` (this mode only) resizes with
+    the antialiased filter that PIL / torchvision ``Resize`` apply when they
+    shrink a photo, so large inputs match what ImageNet models were trained
+    on."""
     from ..server import Servable
 
     if input_format not in ("float_nchw", "uint8_nhwc", "uint8_nhwc_resize"):
         raise ValueError(
             f"input_format must be 'float_nchw', 'uint8_nhwc' or "
             f"'uint8_nhwc_resize', got {input_format!r}")
+    if antialias and input_format != "uint8_nhwc_resize":
+        raise ValueError(
+            "antialias=True needs input_format='uint8_nhwc_resize', got "
+            f"{input_format!r}")
 
     torch.manual_seed(seed)
     model = resnet50().to(device=device, dtype=dtype).eval()
@@ -119,7 +127,8 @@ def resnet50_servable(device: str = "cpu", dtype=torch.float32,
         images_sig = (4, [-1, -1, -1, 3])                   # DT_UINT8
         preprocess = {"images": ImagePreprocess(
             IMAGENET_MEAN, IMAGENET_STD, out_dtype=dtype, layout="nchw",
-            device=device, resize=256, center_crop=224)}
+            device=device, resize=256, center_crop=224,
+            antialias=bool(antialias))}
     else:
         images_sig = (1, [-1, 3, 224, 224])                 # DT_FLOAT
         preprocess = None

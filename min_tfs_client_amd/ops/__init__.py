@@ -172,9 +172,61 @@ def _resize_taps(n_out, offset, ratio, n_in):
     return i0, i1, s - i0.float()
 
 
+def _resize_aa_taps(n_out, offset, ratio, n_in):
+    """Antialiased taps of ``n_out`` output coordinates starting at
+    ``offset`` of the resized axis: ``(lo, size, idx, w)`` with ``idx`` and
+    ``w`` of shape ``[n_out, K]``, ``K`` the longest tap count. Taps past a
+    coordinate's own ``size`` have weight 0 and its last index. fp32 tensor
+    ops, one rounding each."""
+    import numpy as np
+
+    support = ratio if ratio >= 1.0 else 1.0
+    inv = float(np.float32(1.0 / ratio)) if ratio >= 1.0 else 1.0
+    o = torch.arange(offset, offset + n_out, dtype=torch.float32)
+    c = (o + 0.5) * ratio
+    # .to(int64) truncates toward zero
+    lo = ((c - support) + 0.5).to(torch.int64).clamp(0, n_in - 1)
+    hi = ((c + support) + 0.5).to(torch.int64).clamp(max=n_in)
+    size = (hi - lo).clamp(min=1)
+    j = torch.arange(int(size.max()), dtype=torch.int64).view(1, -1)
+    idx = lo.view(-1, 1) + j
+    x = ((idx.float() - c.view(-1, 1)) + 0.5) * inv
+    w = (1.0 - x.abs()).clamp(min=0.0)
+    w = torch.where(j < size.view(-1, 1), w, torch.zeros_like(w))
+    idx = torch.minimum(idx, (lo + size - 1).view(-1, 1))
+    return lo, size, idx, w
+
+
+def _resize_aa_eager(p, rh, rw, top, left, Hc, Wc):
+    """The antialiased recipe on a CPU fp32 ``[N,Hin,Win,C]`` tensor: fp32
+    ``[N,Hc,Wc,C]`` before normalization. Taps are added one at a time in
+    ascending order; a padded tap adds ``0 * p``, which is exact."""
+    _, Hin, Win, _ = p.shape
+    ylo, ysize, yidx, wy = _resize_aa_taps(Hc, top, rh, Hin)
+    _, _, xidx, wx = _resize_aa_taps(Wc, left, rw, Win)
+    y_base = int(ylo[0])
+    p = p[:, y_base:int(ylo[-1] + ysize[-1])]      # the rows the crop needs
+    acc = torch.zeros((p.shape[0], p.shape[1], Wc, p.shape[3]),
+                      dtype=torch.float32)
+    tot = torch.zeros(Wc, dtype=torch.float32)
+    for k in range(wx.shape[1]):
+        wk = wx[:, k]
+        acc = acc + wk.view(1, 1, Wc, 1) * p[:, :, xidx[:, k]]
+        tot = tot + wk
+    h = acc / tot.view(1, 1, Wc, 1)
+    acc = torch.zeros((p.shape[0], Hc, Wc, p.shape[3]), dtype=torch.float32)
+    tot = torch.zeros(Hc, dtype=torch.float32)
+    for k in range(wy.shape[1]):
+        wk = wy[:, k]
+        acc = acc + wk.view(1, Hc, 1, 1) * h[:, yidx[:, k] - y_base]
+        tot = tot + wk
+    return acc / tot.view(1, Hc, 1, 1)
+
+
 def image_u8_resize_to_float(tensor, size, mean, std, crop=None,
                              out_dtype=None, layout="nchw",
-                             pixel_scale=1.0 / 255.0, _variant=0):
+                             pixel_scale=1.0 / 255.0, _variant=0, *,
+                             antialias=False, _ws_cap_bytes=None):
     """Fused uint8 image ingest with bilinear resize and crop: a contiguous
     ``[N,Hin,Win,C]`` uint8 tensor, ``C`` in 1..4, is resized to a virtual
     ``size=(Hr,Wr)`` image, the window ``crop=(top,left,Hc,Wc)`` of that image
@@ -199,7 +251,35 @@ def image_u8_resize_to_float(tensor, size, mean, std, crop=None,
     same window sliced out of the uncropped call, bit for bit. Against
     ``F.interpolate`` the result differs by rounding only.
 
-    Device tensors run the gfx950 kernel (one pass, no eager fallback); CPU
+    ``antialias=True`` (keyword only) switches to the antialiased member of
+    the family, ``F.interpolate(..., antialias=True)``, what PIL and
+    torchvision ``Resize`` do: a separable triangle filter whose width
+    follows the downscale ratio, horizontal pass then vertical pass. For one
+    axis (``o`` the output index plus the crop offset, ``r`` the ``rw`` /
+    ``rh`` above), again one fp32 rounding per operation::
+
+        support = r if r >= 1 else 1
+        inv  = float32(1.0 / r) if r >= 1 else 1
+        c    = (float(o) + 0.5) * r
+        lo   = clamp(int((c - support) + 0.5), 0, n_in - 1)   # truncating
+        hi   = min(int((c + support) + 0.5), n_in)
+        size = max(hi - lo, 1)
+        for j in 0 .. size-1:                   # ascending, acc = tot = 0
+            x   = ((float(lo + j) - c) + 0.5) * inv
+            w   = max(1 - |x|, 0)
+            acc = acc + w * p[lo + j]
+            tot = tot + w
+        value = acc / tot
+
+    The horizontal pass reads the uint8 pixels, the vertical pass its fp32
+    results; then ``y = out_dtype((value * scale_c) + bias_c)``. The identity
+    and crop properties above hold here too. This follows ATen's index rule
+    with one division by ``tot`` instead of normalized weights, so it differs
+    from ``F.interpolate`` by rounding only. An upscaled axis (``r < 1``)
+    keeps support 1, which is plain bilinear.
+
+    Device tensors run the gfx950 kernels (one pass, or two for
+    ``antialias=True``; no eager fallback); CPU
     tensors use an eager expression of exactly these operations, so both are
     bit-identical and CPU-only servers work too. All sides (``Hin``, ``Win``,
     ``Hr``, ``Wr``) must be in 1..16384. Invalid arguments raise
@@ -257,6 +337,10 @@ def image_u8_resize_to_float(tensor, size, mean, std, crop=None,
     scale, bias = normalization_constants(mean, std, pixel_scale)
     rh = float(np.float32(Hin / Hr))
     rw = float(np.float32(Win / Wr))
+    if tensor.is_cuda and antialias:
+        return require_native().u8_nhwc_resize_aa_normalize(
+            tensor, rh, rw, top, left, Hc, Wc, scale, bias, out_dtype,
+            layout == "nchw", int(_ws_cap_bytes or 0))
     if tensor.is_cuda:
         return require_native().u8_nhwc_resize_normalize(
             tensor, rh, rw, top, left, Hc, Wc, scale, bias, out_dtype,
@@ -264,16 +348,19 @@ def image_u8_resize_to_float(tensor, size, mean, std, crop=None,
     if N == 0:
         shape = (0, C, Hc, Wc) if layout == "nchw" else (0, Hc, Wc, C)
         return torch.empty(shape, dtype=out_dtype)
-    y0, y1, wy = _resize_taps(Hc, top, rh, Hin)
-    x0, x1, wx = _resize_taps(Wc, left, rw, Win)
-    p = tensor.float()
-    wx = wx.view(1, 1, Wc, 1)
-    wy = wy.view(1, Hc, 1, 1)
-    r0, r1 = p[:, y0], p[:, y1]
-    p00, p10 = r0[:, :, x0], r1[:, :, x0]
-    t = p00 + wx * (r0[:, :, x1] - p00)
-    b = p10 + wx * (r1[:, :, x1] - p10)
-    v = t + wy * (b - t)
+    if antialias:
+        v = _resize_aa_eager(tensor.float(), rh, rw, top, left, Hc, Wc)
+    else:
+        y0, y1, wy = _resize_taps(Hc, top, rh, Hin)
+        x0, x1, wx = _resize_taps(Wc, left, rw, Win)
+        p = tensor.float()
+        wx = wx.view(1, 1, Wc, 1)
+        wy = wy.view(1, Hc, 1, 1)
+        r0, r1 = p[:, y0], p[:, y1]
+        p00, p10 = r0[:, :, x0], r1[:, :, x0]
+        t = p00 + wx * (r0[:, :, x1] - p00)
+        b = p10 + wx * (r1[:, :, x1] - p10)
+        v = t + wy * (b - t)
     s = torch.tensor(scale, dtype=torch.float32)
     bs = torch.tensor(bias, dtype=torch.float32)
     y = (v * s.view(1, 1, 1, C)) + bs.view(1, 1, 1, C)

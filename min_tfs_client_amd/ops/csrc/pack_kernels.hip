@@ -13,6 +13,8 @@
 //    (server-side preprocessing, so clients ship 1 byte per pixel value),
 //  * the same ingest with a bilinear resize + crop fused in (images of any
 //    size, source taps staged through LDS),
+//  * the antialiased variant of that resize (separable variable-width
+//    triangle filter, horizontal then vertical pass over an fp32 workspace),
 //  * fused masked mean-pool (+ L2 normalize) head: [B,S,H] hidden state ->
 //    fp32 [B,H] sentence embeddings, so responses ship S x fewer bytes,
 // plus the host-side staging machinery: pinned double-buffered
@@ -581,6 +583,45 @@ __device__ __forceinline__ void resize_tap(int o, int offset, float ratio,
   w = __fsub_rn(s, float(i0));
 }
 
+// Store one lane's run: the first min(kResizePx, Wc - ox0) columns of vout
+// (NCHW: [c][k], NHWC: [k][c]) to `dst`, the run's first output element.
+template <typename Out, int C, bool NCHW>
+__device__ __forceinline__ void resize_store_run(
+    const Out (&vout)[C * kResizePx], int ox0, int Wc,
+    Out* __restrict__ dst, int64_t plane) {
+  constexpr int PERV = 16 / int(sizeof(Out));
+  const bool vec = ox0 + kResizePx <= Wc &&
+                   (reinterpret_cast<uintptr_t>(dst) & 15) == 0 &&
+                   (!NCHW || (plane * int64_t(sizeof(Out))) % 16 == 0);
+  if (vec) {
+    if constexpr (NCHW) {
+#pragma unroll
+      for (int c = 0; c < C; ++c)
+#pragma unroll
+        for (int v = 0; v < kResizePx / PERV; ++v)
+          reinterpret_cast<int4*>(dst + c * plane)[v] =
+              *reinterpret_cast<const int4*>(vout + c * kResizePx + v * PERV);
+    } else {
+#pragma unroll
+      for (int v = 0; v < C * kResizePx / PERV; ++v)
+        reinterpret_cast<int4*>(dst)[v] =
+            *reinterpret_cast<const int4*>(vout + v * PERV);
+    }
+  } else {
+    const int span = min(kResizePx, Wc - ox0);
+#pragma unroll
+    for (int k = 0; k < kResizePx; ++k) {
+      if (k < span) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+          if constexpr (NCHW) dst[c * plane + k] = vout[c * kResizePx + k];
+          else dst[k * C + c] = vout[k * C + c];
+        }
+      }
+    }
+  }
+}
+
 // One lane's run: kResizePx output columns from ox0 of one output row. r0/r1
 // point at column `xb` of source rows y0/y1: global memory with xb = 0, or
 // the LDS image of the tile's span with xb = its first column.
@@ -590,7 +631,6 @@ __device__ __forceinline__ void resize_run(
     typename CVT::Out* __restrict__ dst, int64_t plane,
     const U8ResizeParams& p) {
   using Out = typename CVT::Out;
-  constexpr int PERV = 16 / int(sizeof(Out));
   Out vout[C * kResizePx];   // NCHW: [c][k], NHWC: [k][c]
 #pragma unroll
   for (int k = 0; k < kResizePx; ++k) {
@@ -614,36 +654,7 @@ __device__ __forceinline__ void resize_run(
           CVT::cvt(__fadd_rn(__fmul_rn(v, p.scale[c]), p.bias[c]));
     }
   }
-  const bool vec = ox0 + kResizePx <= p.Wc &&
-                   (reinterpret_cast<uintptr_t>(dst) & 15) == 0 &&
-                   (!NCHW || (plane * int64_t(sizeof(Out))) % 16 == 0);
-  if (vec) {
-    if constexpr (NCHW) {
-#pragma unroll
-      for (int c = 0; c < C; ++c)
-#pragma unroll
-        for (int v = 0; v < kResizePx / PERV; ++v)
-          reinterpret_cast<int4*>(dst + c * plane)[v] =
-              *reinterpret_cast<const int4*>(vout + c * kResizePx + v * PERV);
-    } else {
-#pragma unroll
-      for (int v = 0; v < C * kResizePx / PERV; ++v)
-        reinterpret_cast<int4*>(dst)[v] =
-            *reinterpret_cast<const int4*>(vout + v * PERV);
-    }
-  } else {
-    const int span = min(kResizePx, p.Wc - ox0);
-#pragma unroll
-    for (int k = 0; k < kResizePx; ++k) {
-      if (k < span) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-          if constexpr (NCHW) dst[c * plane + k] = vout[c * kResizePx + k];
-          else dst[k * C + c] = vout[k * C + c];
-        }
-      }
-    }
-  }
+  resize_store_run<Out, C, NCHW>(vout, ox0, p.Wc, dst, plane);
 }
 
 template <typename CVT, int C, bool NCHW>
@@ -729,6 +740,204 @@ __global__ void __launch_bounds__(kResizeBlock) u8_nhwc_resize_normalize_kernel(
       resize_run<CVT, C, NCHW>(img + y0 * row_bytes, img + y1 * row_bytes, 0,
                                wy, ox0, dst, plane, p);
     }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// uint8 image ingest with ANTIALIASED resize + crop (separable triangle)
+// ---------------------------------------------------------------------------
+// Same contract as the bilinear section above (uint8 NHWC in, a crop window
+// of a virtual (Hr,Wr) image out, normalized and cast), but a downscale
+// averages every source pixel under a triangle filter whose width follows
+// the ratio: the F.interpolate(mode="bilinear", antialias=True) family, with
+// ATen's _compute_indices_weights_aa index rule and ONE division by the
+// weight sum in place of per-weight normalization. For one axis (input
+// length n_in, ratio r = float(n_in/n_r) from the host, o = output index +
+// crop offset), every line one IEEE fp32 operation, nothing contracted:
+//
+//   support = r >= 1 ? r : 1        inv = r >= 1 ? float(1.0/double(r)) : 1
+//   c    = fmul(fadd(float(o), 0.5), r)
+//   lo   = clamp(int(fadd(fsub(c, support), 0.5)), 0, n_in-1)   int(): trunc
+//   hi   = min(int(fadd(fadd(c, support), 0.5)), n_in)
+//   size = max(hi - lo, 1)
+//   for j = 0 .. size-1, ascending:
+//     x   = fmul(fadd(fsub(float(lo+j), c), 0.5), inv)
+//     w   = max(fsub(1, |x|), 0)
+//     acc = fadd(acc, fmul(w, p[lo+j]))      tot = fadd(tot, w)
+//   value = fdiv(acc, tot)                   IEEE division; tot >= 0.75
+//
+// Horizontal first (uint8 -> fp32), then vertical on those fp32 values, then
+// y = Out(fadd(fmul(v, scale_c), bias_c)). With (Hr,Wr) == (Hin,Win) the
+// weights are exactly (1, 0) and the result is bit-identical to
+// u8_nhwc_normalize_kernel. c, lo and hi are monotone in o (each rounded
+// operation is), so the source rows one crop window needs are the range
+// [lo(first row), lo(last row) + size(last row)): y_base and Rs below.
+//
+// Two kernels, always, in this order on the current stream:
+//
+//  1. u8_resize_aa_h_kernel: a lane owns one (image, source row, output
+//     column) and all C channels of it. It recomputes c/lo/size and each
+//     tap weight on the fly (no weight tables, no per-call H2D), walks its
+//     `size` taps with byte loads straight from global memory (neighbouring
+//     lanes' spans overlap, so the bytes come from L1/L2) and writes C
+//     floats to the fp32 workspace [n, Rs, Wc, C]. Only the Rs source rows
+//     and the Wc cropped columns are computed. The tap loop has a runtime
+//     trip count (up to 32769 at the 16384-side limits).
+//  2. u8_resize_aa_v_kernel: a lane owns kResizePx = 8 consecutive output
+//     columns of one output row, all channels: 8*C contiguous floats per
+//     workspace row, loaded as 16 B vectors when the run is whole and the
+//     address is 16 B-aligned (every workspace row is when Wc*C % 4 == 0),
+//     else as scalars with the column clamped (duplicates are never
+//     stored). It accumulates the `size` rows in ascending order, divides,
+//     normalizes, casts and stores with resize_store_run (16 B vectors, or
+//     scalars for a ragged run or a misaligned destination/plane).
+//
+// Both grids: 256-thread workgroups, min(ceil(lanes/256), 2048) of them,
+// grid-stride over lanes. The workspace holds Rs*Wc*C floats per image and
+// is capped (kResizeAAWsBytes); a batch that needs more runs in chunks of
+// whole images through one workspace, each chunk both kernels. An image is
+// computed the same way whichever chunk it lands in.
+constexpr int kResizeAABlock = 256;
+
+struct U8ResizeAAParams {
+  float scale[4];
+  float bias[4];
+  float rh, rw;          // ratios
+  float sup_h, sup_w;    // filter support per axis: max(r, 1)
+  float inv_h, inv_w;    // 1/support, rounded once on the host
+  int Hin, Win, Hc, Wc, top, left;
+  int y_base, Rs;        // first source row of the workspace, and its rows
+};
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define AA_MUL(a, b) __fmul_rn((a), (b))
+#define AA_ADD(a, b) __fadd_rn((a), (b))
+#define AA_SUB(a, b) __fsub_rn((a), (b))
+#else  // host: this file is built with -ffp-contract=off
+#define AA_MUL(a, b) ((a) * (b))
+#define AA_ADD(a, b) ((a) + (b))
+#define AA_SUB(a, b) ((a) - (b))
+#endif
+
+// Centre, first tap and tap count of coordinate `o` of the resized axis.
+// Also run on the host, for the workspace's row range.
+__host__ __device__ __forceinline__ void aa_span(int o, float r, float support,
+                                                 int n_in, float& c, int& lo,
+                                                 int& size) {
+  c = AA_MUL(AA_ADD(float(o), 0.5f), r);
+  const int l = int(AA_ADD(AA_SUB(c, support), 0.5f));
+  const int h = int(AA_ADD(AA_ADD(c, support), 0.5f));
+  lo = l < 0 ? 0 : (l > n_in - 1 ? n_in - 1 : l);
+  const int hi = h < n_in ? h : n_in;
+  size = hi - lo > 1 ? hi - lo : 1;
+}
+
+__device__ __forceinline__ float aa_weight(int i, float c, float inv) {
+  const float x = __fmul_rn(__fadd_rn(__fsub_rn(float(i), c), 0.5f), inv);
+  return fmaxf(__fsub_rn(1.f, fabsf(x)), 0.f);
+}
+
+template <int C>
+__global__ void __launch_bounds__(kResizeAABlock) u8_resize_aa_h_kernel(
+    const uint8_t* __restrict__ in, float* __restrict__ ws, int64_t N,
+    U8ResizeAAParams p) {
+  const int64_t row_bytes = int64_t(p.Win) * C;
+  const int64_t lanes = N * p.Rs * p.Wc;
+  const int64_t stride = int64_t(gridDim.x) * kResizeAABlock;
+  for (int64_t idx = int64_t(blockIdx.x) * kResizeAABlock + threadIdx.x;
+       idx < lanes; idx += stride) {
+    const int ox = int(idx % p.Wc);
+    const int64_t t = idx / p.Wc;
+    const int s = int(t % p.Rs);
+    const int64_t n = t / p.Rs;
+    float c;
+    int lo, size;
+    aa_span(ox + p.left, p.rw, p.sup_w, p.Win, c, lo, size);
+    // lo + size <= Win and y_base + Rs <= Hin: every tap is inside the image
+    const uint8_t* src =
+        in + (n * p.Hin + p.y_base + s) * row_bytes + int64_t(lo) * C;
+    float acc[C];
+#pragma unroll
+    for (int ch = 0; ch < C; ++ch) acc[ch] = 0.f;
+    float tot = 0.f;
+    for (int j = 0; j < size; ++j) {
+      const float w = aa_weight(lo + j, c, p.inv_w);
+#pragma unroll
+      for (int ch = 0; ch < C; ++ch)
+        acc[ch] = __fadd_rn(acc[ch], __fmul_rn(w, float(src[j * C + ch])));
+      tot = __fadd_rn(tot, w);
+    }
+    float* dst = ws + idx * C;   // [n][s][ox][ch]
+#pragma unroll
+    for (int ch = 0; ch < C; ++ch) dst[ch] = __fdiv_rn(acc[ch], tot);
+  }
+}
+
+template <typename CVT, int C, bool NCHW>
+__global__ void __launch_bounds__(kResizeAABlock) u8_resize_aa_v_kernel(
+    const float* __restrict__ ws, typename CVT::Out* __restrict__ out,
+    int64_t N, U8ResizeAAParams p) {
+  using Out = typename CVT::Out;
+  constexpr int L = kResizePx * C;       // floats per workspace row and lane
+  static_assert(kResizePx % (16 / int(sizeof(Out))) == 0,
+                "a lane run must fill whole 16 B stores");
+  const int runs = (p.Wc + kResizePx - 1) / kResizePx;
+  const int64_t plane = int64_t(p.Hc) * p.Wc;
+  const int64_t row_floats = int64_t(p.Wc) * C;
+  const int64_t lanes = N * p.Hc * runs;
+  const int64_t stride = int64_t(gridDim.x) * kResizeAABlock;
+  for (int64_t idx = int64_t(blockIdx.x) * kResizeAABlock + threadIdx.x;
+       idx < lanes; idx += stride) {
+    const int ox0 = int(idx % runs) * kResizePx;
+    const int64_t t = idx / runs;
+    const int oy = int(t % p.Hc);
+    const int64_t n = t / p.Hc;
+    float c;
+    int lo, size;
+    aa_span(oy + p.top, p.rh, p.sup_h, p.Hin, c, lo, size);
+    // y_base <= lo and lo + size <= y_base + Rs (monotone in oy)
+    const float* src =
+        ws + ((n * p.Rs + (lo - p.y_base)) * p.Wc + ox0) * C;
+    const int valid = min(kResizePx, p.Wc - ox0) * C;   // floats of this run
+    float acc[L];
+#pragma unroll
+    for (int e = 0; e < L; ++e) acc[e] = 0.f;
+    float tot = 0.f;
+    if (valid == L && (reinterpret_cast<uintptr_t>(src) & 15) == 0 &&
+        row_floats % 4 == 0) {
+      for (int j = 0; j < size; ++j, src += row_floats) {
+        const float w = aa_weight(lo + j, c, p.inv_h);
+        float v[L];
+#pragma unroll
+        for (int q = 0; q < L / 4; ++q)
+          reinterpret_cast<float4*>(v)[q] =
+              reinterpret_cast<const float4*>(src)[q];
+#pragma unroll
+        for (int e = 0; e < L; ++e)
+          acc[e] = __fadd_rn(acc[e], __fmul_rn(w, v[e]));
+        tot = __fadd_rn(tot, w);
+      }
+    } else {
+      for (int j = 0; j < size; ++j, src += row_floats) {
+        const float w = aa_weight(lo + j, c, p.inv_h);
+#pragma unroll
+        for (int e = 0; e < L; ++e)
+          acc[e] = __fadd_rn(acc[e], __fmul_rn(w, src[min(e, valid - 1)]));
+        tot = __fadd_rn(tot, w);
+      }
+    }
+    Out vout[L];   // NCHW: [c][k], NHWC: [k][c]
+#pragma unroll
+    for (int k = 0; k < kResizePx; ++k)
+#pragma unroll
+      for (int ch = 0; ch < C; ++ch)
+        vout[NCHW ? ch * kResizePx + k : k * C + ch] = CVT::cvt(__fadd_rn(
+            __fmul_rn(__fdiv_rn(acc[k * C + ch], tot), p.scale[ch]),
+            p.bias[ch]));
+    Out* dst = NCHW
+        ? out + (n * C * p.Hc + oy) * p.Wc + ox0
+        : out + ((n * p.Hc + oy) * p.Wc + ox0) * C;
+    resize_store_run<Out, C, NCHW>(vout, ox0, p.Wc, dst, plane);
   }
 }
 
@@ -1305,6 +1514,133 @@ at::Tensor u8_nhwc_resize_normalize(
   else if (out_dtype == at::kBFloat16) by_channels(F32ToBf16{});
   else by_channels(F32ToF16{});
   HIP_CHECK(hipGetLastError());
+  return out;
+}
+
+// uint8 NHWC ingest with antialiased resize + crop; see the kernel section
+// for semantics and paths. Arguments as u8_nhwc_resize_normalize.
+// `ws_cap_bytes` > 0 overrides the workspace cap (tests reach the chunked
+// loop with it at tiny shapes); a chunk always holds at least one image.
+//
+// The cap, 256 MiB: the workspace of a (1080,1920) photo shrunk to short
+// side 256 with the 224 centre crop is 950 rows x 224 columns x 3 floats,
+// 2.55 MB, so a hundred such images still run as one chunk, and the block is
+// 0.1 % of the 288 GB of HBM. Beyond it the launches (microseconds each) are
+// noise against the filtering a chunk of that size holds.
+//
+// Measured on MI355X, interleaved rounds in one process, u8 -> bf16 NCHW,
+// this path vs the eager device chain (permute+float, F.interpolate with
+// antialias=True, slice, normalize, cast) vs the bilinear kernel above:
+//   (32,1080,1920,3) -> (256,455), 224 crop   93.4 vs 1820.5 vs 57.0 us
+//   (1,1080,1920,3)  -> (256,455), 224 crop   12.2 vs   72.2 vs  8.2 us
+//   (32,256,341,3)   -> (128,170)             38.0 vs  106.1 vs 10.8 us
+// The horizontal pass gathers its taps from global memory; staging the
+// source spans through LDS has not been tried, so there is no second number.
+constexpr int64_t kResizeAAWsBytes = int64_t(256) << 20;
+
+at::Tensor u8_nhwc_resize_aa_normalize(
+    const at::Tensor& in, double rh, double rw, int64_t top, int64_t left,
+    int64_t Hc, int64_t Wc, std::vector<double> scale,
+    std::vector<double> bias, at::ScalarType out_dtype, bool out_nchw,
+    int64_t ws_cap_bytes) {
+  TORCH_CHECK(in.is_cuda() && in.dim() == 4 && in.is_contiguous() &&
+              in.scalar_type() == at::kByte,
+              "u8_nhwc_resize_aa_normalize expects a contiguous uint8 device "
+              "tensor [N,H,W,C]");
+  const int64_t N = in.size(0), Hin = in.size(1), Win = in.size(2),
+                C = in.size(3);
+  constexpr int64_t kMaxSide = 16384;
+  TORCH_CHECK(C >= 1 && C <= 4,
+              "u8_nhwc_resize_aa_normalize: C must be in 1..4");
+  TORCH_CHECK(Hin >= 1 && Hin <= kMaxSide && Win >= 1 && Win <= kMaxSide,
+              "u8_nhwc_resize_aa_normalize: input sides must be in 1..16384");
+  TORCH_CHECK(Hc >= 1 && Wc >= 1 && top >= 0 && left >= 0 &&
+              top + Hc <= kMaxSide && left + Wc <= kMaxSide,
+              "u8_nhwc_resize_aa_normalize: bad crop window");
+  // a ratio is float(n_in / n_r) with both sides in 1..16384
+  TORCH_CHECK(rh > 0.0 && rw > 0.0 && rh <= double(kMaxSide) &&
+              rw <= double(kMaxSide),
+              "u8_nhwc_resize_aa_normalize: ratios must be in (0, 16384]");
+  TORCH_CHECK(int64_t(scale.size()) == C && int64_t(bias.size()) == C,
+              "u8_nhwc_resize_aa_normalize: scale/bias need one value per "
+              "channel");
+  TORCH_CHECK(out_dtype == at::kFloat || out_dtype == at::kBFloat16 ||
+              out_dtype == at::kHalf,
+              "u8_nhwc_resize_aa_normalize: out_dtype must be f32, bf16 or "
+              "f16");
+  auto out = out_nchw
+      ? at::empty({N, C, Hc, Wc}, in.options().dtype(out_dtype))
+      : at::empty({N, Hc, Wc, C}, in.options().dtype(out_dtype));
+  if (N == 0) return out;  // zero grid: never launch
+
+  U8ResizeAAParams p{};
+  for (int64_t c = 0; c < C; ++c) {
+    p.scale[c] = float(scale[c]);
+    p.bias[c] = float(bias[c]);
+  }
+  p.rh = float(rh);
+  p.rw = float(rw);
+  p.sup_h = p.rh >= 1.f ? p.rh : 1.f;
+  p.sup_w = p.rw >= 1.f ? p.rw : 1.f;
+  p.inv_h = p.rh >= 1.f ? float(1.0 / double(p.rh)) : 1.f;
+  p.inv_w = p.rw >= 1.f ? float(1.0 / double(p.rw)) : 1.f;
+  p.Hin = int(Hin); p.Win = int(Win);
+  p.Hc = int(Hc); p.Wc = int(Wc);
+  p.top = int(top); p.left = int(left);
+  // source rows of the crop window: [lo(first row), lo(last) + size(last))
+  float unused_c;
+  int lo_first, lo_last, size_first, size_last;
+  aa_span(p.top, p.rh, p.sup_h, p.Hin, unused_c, lo_first, size_first);
+  aa_span(p.top + p.Hc - 1, p.rh, p.sup_h, p.Hin, unused_c, lo_last,
+          size_last);
+  p.y_base = lo_first;
+  p.Rs = lo_last + size_last - lo_first;
+  TORCH_CHECK(p.Rs >= 1 && p.y_base + p.Rs <= p.Hin,
+              "u8_nhwc_resize_aa_normalize: internal row range error");
+
+  const int64_t cap = ws_cap_bytes > 0 ? ws_cap_bytes : kResizeAAWsBytes;
+  const int64_t img_floats = int64_t(p.Rs) * Wc * C;
+  const int64_t chunk = std::max<int64_t>(
+      1, std::min<int64_t>(N, cap / (img_floats * int64_t(sizeof(float)))));
+  auto ws = at::empty({chunk * img_floats}, in.options().dtype(at::kFloat));
+  const int64_t runs = (Wc + kResizePx - 1) / kResizePx;
+  const int64_t in_img = Hin * Win * C, out_img = C * Hc * Wc;
+  const auto* src = static_cast<const uint8_t*>(in.const_data_ptr());
+
+  auto launch = [&](auto cvt_tag, auto c_tag, auto nchw_tag) {
+    using CVT = decltype(cvt_tag);
+    constexpr int CC = decltype(c_tag)::value;
+    auto* dst = reinterpret_cast<typename CVT::Out*>(out.mutable_data_ptr());
+    for (int64_t n0 = 0; n0 < N; n0 += chunk) {
+      const int64_t n = std::min(chunk, N - n0);
+      hipLaunchKernelGGL(
+          (u8_resize_aa_h_kernel<CC>),
+          dim3(grid_for(n * p.Rs * Wc, kResizeAABlock)), dim3(kResizeAABlock),
+          0, current_stream(), src + n0 * in_img, ws.data_ptr<float>(), n, p);
+      HIP_CHECK(hipGetLastError());
+      hipLaunchKernelGGL(
+          (u8_resize_aa_v_kernel<CVT, CC, decltype(nchw_tag)::value>),
+          dim3(grid_for(n * Hc * runs, kResizeAABlock)), dim3(kResizeAABlock),
+          0, current_stream(), ws.data_ptr<float>(), dst + n0 * out_img, n,
+          p);
+      HIP_CHECK(hipGetLastError());
+    }
+  };
+  auto by_layout = [&](auto cvt_tag, auto c_tag) {
+    if (out_nchw) launch(cvt_tag, c_tag, std::true_type{});
+    else launch(cvt_tag, c_tag, std::false_type{});
+  };
+  auto by_channels = [&](auto cvt_tag) {
+    switch (C) {
+      case 1: by_layout(cvt_tag, std::integral_constant<int, 1>{}); break;
+      case 2: by_layout(cvt_tag, std::integral_constant<int, 2>{}); break;
+      case 3: by_layout(cvt_tag, std::integral_constant<int, 3>{}); break;
+      default: by_layout(cvt_tag, std::integral_constant<int, 4>{});
+    }
+  };
+  if (out_dtype == at::kFloat) by_channels(IdF32{});
+  else if (out_dtype == at::kBFloat16) by_channels(F32ToBf16{});
+  else by_channels(F32ToF16{});
   return out;
 }
 

@@ -7,7 +7,8 @@ the tensor a client sent for that alias into what the model eats.
 runs the fused dequantize + normalize + NCHW kernel
 (``ops.image_u8_to_float``), or, with ``resize`` / ``center_crop`` set, the
 fused bilinear resize + crop + normalize + NCHW kernel
-(``ops.image_u8_resize_to_float``) on images of any size.
+(``ops.image_u8_resize_to_float``) on images of any size; ``antialias=True``
+selects the antialiased resize kernels for downscaled photos.
 """
 from __future__ import annotations
 
@@ -66,11 +67,14 @@ class ImagePreprocess:
       ``top = (Hr - Hc) // 2``, ``left = (Wr - Wc) // 2`` of the resized
       ``(Hr, Wr)`` image. A crop larger than the resized image raises
       ``ValueError``. Without ``resize`` the input is cropped at its own
-      size."""
+      size.
+    * ``antialias=True`` resizes with the antialiased triangle filter (what
+      PIL and torchvision ``Resize`` do when they shrink an image) instead of
+      the 2-tap bilinear. It needs ``resize`` or ``center_crop``."""
 
     def __init__(self, mean, std, out_dtype=None, layout: str = "nchw",
                  pixel_scale: float = 1.0 / 255.0, device=None,
-                 resize=None, center_crop=None):
+                 resize=None, center_crop=None, antialias: bool = False):
         self.mean = tuple(float(m) for m in mean)
         self.std = tuple(float(s) for s in std)
         self.out_dtype = torch.float32 if out_dtype is None else out_dtype
@@ -85,6 +89,11 @@ class ImagePreprocess:
         self.resize = _int_or_pair(resize, "resize")
         crop = _int_or_pair(center_crop, "center_crop")
         self.center_crop = (crop, crop) if isinstance(crop, int) else crop
+        self.antialias = bool(antialias)
+        if self.antialias and self.resize is None and self.center_crop is None:
+            raise ValueError(
+                "antialias=True needs resize or center_crop: without them "
+                "the input is not resized")
 
     def resized_size(self, height: int, width: int):
         """``(Hr, Wr)`` of the resized image for an input of this size."""
@@ -134,4 +143,4 @@ class ImagePreprocess:
         return ops.image_u8_resize_to_float(
             x, size, self.mean, self.std, crop=self.crop_window(*size),
             out_dtype=self.out_dtype, layout=self.layout,
-            pixel_scale=self.pixel_scale)
+            pixel_scale=self.pixel_scale, antialias=self.antialias)

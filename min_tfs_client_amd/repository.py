@@ -17,8 +17,10 @@ On-disk version-directory formats understood by the default loader:
                                "device": ..., "state_dict": "weights.pt"?}
                                plus optional I/O modes: "input_format"
                                (resnet50: "float_nchw", "uint8_nhwc" or
-                               "uint8_nhwc_resize"), "output_format" and
-                               "normalize_embedding" (bert_base)
+                               "uint8_nhwc_resize") and "antialias"
+                               (resnet50, with "uint8_nhwc_resize"),
+                               "output_format" and "normalize_embedding"
+                               (bert_base)
   * ``model.pt``            — TorchScript module (torch.jit.load)
 plus TF-style ``assets.extra/tf_serving_warmup_requests`` (a TFRecord of
 serialized PredictionLog protos — framing per TF's RecordWriter: length,
@@ -167,7 +169,8 @@ def default_loader(name: str, version_dir: str,
         # present; an unknown value is the factory's ValueError
         if family == "resnet50":
             from .models import resnet50_servable
-            modes = {k: cfg[k] for k in ("input_format",) if k in cfg}
+            modes = {k: cfg[k] for k in ("input_format", "antialias")
+                     if k in cfg}
             servable = resnet50_servable(device, **modes)
         elif family == "bert_base":
             from .models import bert_servable
