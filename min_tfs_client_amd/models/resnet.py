@@ -8,7 +8,8 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from ..preprocess import IMAGENET_MEAN, IMAGENET_STD, ImagePreprocess
+from ..preprocess import (IMAGENET_MEAN, IMAGENET_STD, ImagePreprocess,
+                          RaggedImagePreprocess)
 
 
 class Bottleneck(nn.Module):
@@ -93,13 +94,27 @@ def resnet50_servable(device: str = "cpu", dtype=torch.float32,
     request share one size. ``antialias=True`` (this mode only) resizes with
     the antialiased filter that PIL / torchvision ``Resize`` apply when they
     shrink a photo, so large inputs match what ImageNet models were trained
-    on."""
+    on.
+    ``input_format="uint8_ragged"``: one request carries N photos of N
+    different sizes. "images" is DT_UINT8 [total_bytes], the HWC pixels of
+    the images back to back with no padding, and "image_shapes" is DT_INT32
+    (N,2), row i being (H_i, W_i) (``preprocess.pack_ragged_images`` builds
+    both). One kernel launch resizes each image's shorter side to 256, takes
+    its 224x224 centre crop and normalizes
+    (``RaggedImagePreprocess(resize=256, center_crop=224)``); every image
+    gets exactly what the ``uint8_nhwc_resize`` mode gives it alone.
+    ``antialias=True`` is not available in this mode."""
     from ..server import Servable
 
-    if input_format not in ("float_nchw", "uint8_nhwc", "uint8_nhwc_resize"):
+    if input_format not in ("float_nchw", "uint8_nhwc", "uint8_nhwc_resize",
+                            "uint8_ragged"):
         raise ValueError(
-            f"input_format must be 'float_nchw', 'uint8_nhwc' or "
-            f"'uint8_nhwc_resize', got {input_format!r}")
+            f"input_format must be 'float_nchw', 'uint8_nhwc', "
+            f"'uint8_nhwc_resize' or 'uint8_ragged', got {input_format!r}")
+    if antialias and input_format == "uint8_ragged":
+        raise ValueError(
+            "antialias=True is not supported with input_format="
+            "'uint8_ragged': antialiased ragged batches are not implemented")
     if antialias and input_format != "uint8_nhwc_resize":
         raise ValueError(
             "antialias=True needs input_format='uint8_nhwc_resize', got "
@@ -129,14 +144,22 @@ def resnet50_servable(device: str = "cpu", dtype=torch.float32,
             IMAGENET_MEAN, IMAGENET_STD, out_dtype=dtype, layout="nchw",
             device=device, resize=256, center_crop=224,
             antialias=bool(antialias))}
+    elif input_format == "uint8_ragged":
+        images_sig = (4, [-1])                              # DT_UINT8
+        preprocess = {("images", "image_shapes"): RaggedImagePreprocess(
+            IMAGENET_MEAN, IMAGENET_STD, out_dtype=dtype, layout="nchw",
+            device=device, resize=256, center_crop=224)}
     else:
         images_sig = (1, [-1, 3, 224, 224])                 # DT_FLOAT
         preprocess = None
+    sig_inputs = {"images": images_sig}
+    if input_format == "uint8_ragged":
+        sig_inputs["image_shapes"] = (3, [-1, 2])           # DT_INT32
     s = Servable(
         fn,
         signature={
             "method_name": "tensorflow/serving/predict",
-            "inputs": {"images": images_sig},
+            "inputs": sig_inputs,
             "outputs": {"logits": (1, [-1, 1000])},
         },
         preprocess=preprocess)

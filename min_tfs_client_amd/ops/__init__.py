@@ -369,6 +369,188 @@ def image_u8_resize_to_float(tensor, size, mean, std, crop=None,
     return y.to(out_dtype).contiguous()
 
 
+def _ragged_pairs(value, n, what, name):
+    """``value`` as an int64 numpy ``[n,2]``: one pair for every image, or
+    one pair per image."""
+    import numpy as np
+
+    if isinstance(value, torch.Tensor):
+        value = value.cpu().numpy()
+    try:
+        arr = np.asarray(value)
+    except (TypeError, ValueError):
+        arr = None
+    if arr is None or arr.dtype.kind not in "iu" or \
+            arr.shape not in ((2,), (n, 2)):
+        raise ValueError(
+            f"{name}: {what} must be one integer pair or integer [{n},2], "
+            f"got {value!r}")
+    arr = arr.astype(np.int64)
+    if arr.ndim == 1:
+        arr = np.broadcast_to(arr, (n, 2))
+    return arr
+
+
+def _first_bad(mask):
+    import numpy as np
+
+    idx = np.nonzero(mask)[0]
+    return int(idx[0]) if idx.size else None
+
+
+def image_u8_ragged_resize_to_float(data, shapes, sizes, out_size, mean, std,
+                                    origins=None, out_dtype=None,
+                                    layout="nchw", pixel_scale=1.0 / 255.0):
+    """Fused uint8 image ingest of a ragged batch: N images of N different
+    sizes, packed back to back with no padding, are each resized, cropped to
+    one shared output size and normalized into one ``[N,C,Hc,Wc]``
+    (``layout="nhwc"``: ``[N,Hc,Wc,C]``) batch, in one kernel launch.
+
+    * ``data``: contiguous 1-D uint8 torch tensor, on CPU or device. Image
+      ``i`` is HWC and starts at byte ``off_i = sum_{j<i} H_j*W_j*C``.
+    * ``shapes``: integer ``[N,2]``, row ``i`` is ``(H_i, W_i)``. It is read
+      on the **host**: a list, a numpy array or a CPU tensor. A device
+      tensor is accepted and copied to the host, which costs a small
+      synchronizing D2H copy per call.
+    * ``sizes``: the resized size, one ``(Hr,Wr)`` pair for all images or
+      ``[N,2]`` per image.
+    * ``out_size``: the shared ``(Hc,Wc)``.
+    * ``origins``: ``(top,left)`` of the crop window inside the resized
+      image, ``[N,2]`` per image, one pair, or ``None`` for zeros.
+    * ``C = len(mean)``, in 1..4.
+
+    The contract, bit for bit::
+
+        out[i] == image_u8_resize_to_float(
+                      data[off_i : off_i + H_i*W_i*C].view(1,H_i,W_i,C),
+                      sizes[i], mean, std,
+                      crop=(top_i, left_i, Hc, Wc), out_dtype=out_dtype,
+                      layout=layout, pixel_scale=pixel_scale)[0]
+
+    CPU tensors run exactly this loop, so CPU-only servers work. Device
+    tensors run the gfx950 ragged kernel only (no eager fallback): the host
+    builds a per-image table (offset, sizes, origin, ``float32(H_i/Hr_i)``,
+    ``float32(W_i/Wr_i)``) and copies it on the current stream from a pinned
+    buffer. Antialiased resizing is not available for ragged batches.
+
+    Invalid arguments raise ``ValueError`` on both paths, before any launch,
+    and name the image at fault: wrong dtype, rank or contiguity of ``data``;
+    ``shapes`` not integer ``[N,2]``; ``len(mean) != len(std)`` or C outside
+    1..4; a side outside 1..16384; ``sum(H_i*W_i*C) != data.numel()``;
+    ``sizes`` / ``origins`` of the wrong shape; a crop window not inside an
+    image's resized size; a bad ``layout`` or ``out_dtype``. ``N == 0`` with
+    empty ``data`` returns an empty tensor of the output shape."""
+    import numpy as np
+
+    name = "image_u8_ragged_resize_to_float"
+    if out_dtype is None:
+        out_dtype = torch.float32
+    if layout not in ("nchw", "nhwc"):
+        raise ValueError(f"layout must be 'nchw' or 'nhwc', got {layout!r}")
+    if out_dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError(
+            f"out_dtype must be float32, bfloat16 or float16, got {out_dtype}")
+    if not isinstance(data, torch.Tensor):
+        raise ValueError(f"{name} expects a torch tensor")
+    if data.dtype != torch.uint8:
+        raise ValueError(f"{name} expects uint8 pixels, got {data.dtype}")
+    if data.dim() != 1:
+        raise ValueError(
+            f"{name} expects a flat [total_bytes] tensor, got rank "
+            f"{data.dim()}")
+    if not data.is_contiguous():
+        raise ValueError(f"{name} expects a contiguous tensor")
+    if len(mean) != len(std):
+        raise ValueError(
+            f"mean has {len(mean)} entries but std has {len(std)}")
+    C = len(mean)
+    if not 1 <= C <= 4:
+        raise ValueError(f"{name} supports 1..4 channels, got {C}")
+
+    if isinstance(shapes, torch.Tensor):
+        shapes = shapes.cpu().numpy()      # device tensor: synchronizing D2H
+    try:
+        shp = np.asarray(shapes)
+    except (TypeError, ValueError):
+        shp = None
+    if shp is not None and shp.size == 0 and shp.ndim <= 2:
+        shp = np.zeros((0, 2), dtype=np.int64)         # [] or [0,2]
+    if shp is None or shp.dtype.kind not in "iu" or shp.ndim != 2 or \
+            shp.shape[1] != 2:
+        raise ValueError(
+            f"{name}: shapes must be integer [N,2] rows of (H, W), got "
+            f"{shapes!r}")
+    shp = shp.astype(np.int64)
+    N = int(shp.shape[0])
+    try:
+        Hc, Wc = (int(d) for d in out_size)
+    except (TypeError, ValueError):
+        raise ValueError(
+            f"out_size must be (H, W), got {out_size!r}") from None
+    if not (1 <= Hc <= RESIZE_MAX_SIDE and 1 <= Wc <= RESIZE_MAX_SIDE):
+        raise ValueError(
+            f"{name}: out_size sides must be in 1..{RESIZE_MAX_SIDE}, got "
+            f"{Hc}x{Wc}")
+    siz = _ragged_pairs(sizes, N, "sizes", name)
+    org = (np.zeros((N, 2), dtype=np.int64) if origins is None
+           else _ragged_pairs(origins, N, "origins", name))
+
+    for label, arr in (("input", shp), ("resized", siz)):
+        bad = _first_bad(((arr < 1) | (arr > RESIZE_MAX_SIDE)).any(axis=1))
+        if bad is not None:
+            raise ValueError(
+                f"{name}: image {bad}: {label} sides must be in "
+                f"1..{RESIZE_MAX_SIDE}, got {int(arr[bad, 0])}x"
+                f"{int(arr[bad, 1])}")
+    nbytes = shp[:, 0] * shp[:, 1] * C
+    total = int(nbytes.sum())
+    if total != data.numel():
+        raise ValueError(
+            f"{name}: shapes describe {total} bytes ({N} images, {C} "
+            f"channels) but data has {data.numel()}")
+    bad = _first_bad((org < 0).any(axis=1) | (org[:, 0] + Hc > siz[:, 0]) |
+                     (org[:, 1] + Wc > siz[:, 1]))
+    if bad is not None:
+        raise ValueError(
+            f"{name}: image {bad}: crop window (top={int(org[bad, 0])}, "
+            f"left={int(org[bad, 1])}, {Hc}x{Wc}) is not inside the resized "
+            f"image {int(siz[bad, 0])}x{int(siz[bad, 1])}")
+    scale, bias = normalization_constants(mean, std, pixel_scale)
+    offsets = np.zeros(N, dtype=np.int64)
+    np.cumsum(nbytes[:-1], out=offsets[1:])
+
+    if data.is_cuda:
+        native = require_native()
+        # the kernel's per-image table, int32 [N,8]: offset (int64 as two
+        # little-endian words), Hin, Win, top, left, bits of rh, bits of rw
+        table = torch.empty((N, 8), dtype=torch.int32, pin_memory=N > 0)
+        t = table.numpy()
+        t[:, 0:2] = offsets.astype("<i8").view("<i4").reshape(N, 2)
+        t[:, 2:4] = shp
+        t[:, 4:6] = org
+        # Python-double division rounded once to fp32, as the dense op does
+        t[:, 6:8] = (shp / siz).astype(np.float32).view(np.int32)
+        # pinned source: the copy is queued on the current stream and the
+        # caching host allocator keeps the buffer until it has completed
+        table_dev = table.to(data.device, non_blocking=True)
+        return native.u8_ragged_resize_normalize(
+            data, table_dev, C, Hc, Wc, scale, bias, out_dtype,
+            layout == "nchw")
+    if N == 0:
+        shape = (0, C, Hc, Wc) if layout == "nchw" else (0, Hc, Wc, C)
+        return torch.empty(shape, dtype=out_dtype)
+    outs = []
+    for i in range(N):
+        h, w = int(shp[i, 0]), int(shp[i, 1])
+        off = int(offsets[i])
+        outs.append(image_u8_resize_to_float(
+            data[off:off + h * w * C].view(1, h, w, C),
+            (int(siz[i, 0]), int(siz[i, 1])), mean, std,
+            crop=(int(org[i, 0]), int(org[i, 1]), Hc, Wc),
+            out_dtype=out_dtype, layout=layout, pixel_scale=pixel_scale))
+    return torch.cat(outs)
+
+
 def masked_mean_pool(hidden, mask=None, normalize=False):
     """Fused masked mean-pool head: ``[B,S,H]`` hidden state (f32, bf16 or
     f16, contiguous) -> fp32 ``[B,H]``, one vector per sequence.

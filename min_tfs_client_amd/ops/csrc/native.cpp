@@ -35,6 +35,10 @@ at::Tensor u8_nhwc_resize_normalize(
     int64_t Hc, int64_t Wc, std::vector<double> scale,
     std::vector<double> bias, at::ScalarType out_dtype, bool out_nchw,
     int64_t variant);
+at::Tensor u8_ragged_resize_normalize(
+    const at::Tensor& in, const at::Tensor& table, int64_t C, int64_t Hc,
+    int64_t Wc, std::vector<double> scale, std::vector<double> bias,
+    at::ScalarType out_dtype, bool out_nchw);
 at::Tensor u8_nhwc_resize_aa_normalize(
     const at::Tensor& in, double rh, double rw, int64_t top, int64_t left,
     int64_t Hc, int64_t Wc, std::vector<double> scale,
@@ -644,6 +648,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("left"), py::arg("crop_h"), py::arg("crop_w"),
         py::arg("scale"), py::arg("bias"), py::arg("out_dtype"),
         py::arg("out_nchw") = true, py::arg("variant") = 0);
+  m.def("u8_ragged_resize_normalize", &mi355x::u8_ragged_resize_normalize,
+        py::arg("input"), py::arg("table"), py::arg("channels"),
+        py::arg("crop_h"), py::arg("crop_w"), py::arg("scale"),
+        py::arg("bias"), py::arg("out_dtype"), py::arg("out_nchw") = true);
   m.def("u8_nhwc_resize_aa_normalize", &mi355x::u8_nhwc_resize_aa_normalize,
         py::arg("input"), py::arg("rh"), py::arg("rw"), py::arg("top"),
         py::arg("left"), py::arg("crop_h"), py::arg("crop_w"),

@@ -9,6 +9,10 @@ runs the fused dequantize + normalize + NCHW kernel
 fused bilinear resize + crop + normalize + NCHW kernel
 (``ops.image_u8_resize_to_float``) on images of any size; ``antialias=True``
 selects the antialiased resize kernels for downscaled photos.
+``RaggedImagePreprocess`` is the mixed-size case: one request carries N
+images of N different sizes packed back to back (``pack_ragged_images``) and
+one kernel launch (``ops.image_u8_ragged_resize_to_float``) turns them into
+one batch.
 """
 from __future__ import annotations
 
@@ -44,6 +48,20 @@ def _int_or_pair(value, what):
             raise ValueError(f"{what} must be an int or (H, W), got {value!r}")
         return (_positive_int(value[0], what), _positive_int(value[1], what))
     return _positive_int(value, what)
+
+
+def _as_tensor(x):
+    if isinstance(x, torch.Tensor):
+        return x
+    arr = np.asarray(x)
+    if arr.dtype.kind in ("S", "U", "O"):
+        raise ValueError(
+            f"image input must be uint8 pixels, got {arr.dtype}")
+    with warnings.catch_warnings():
+        # decoded request arrays are read-only views of the wire bytes;
+        # they are only read here
+        warnings.simplefilter("ignore", UserWarning)
+        return torch.from_numpy(arr)
 
 
 class ImagePreprocess:
@@ -119,16 +137,7 @@ class ImagePreprocess:
                 hc, wc)
 
     def __call__(self, x):
-        if not isinstance(x, torch.Tensor):
-            arr = np.asarray(x)
-            if arr.dtype.kind in ("S", "U", "O"):
-                raise ValueError(
-                    f"image input must be uint8 pixels, got {arr.dtype}")
-            with warnings.catch_warnings():
-                # decoded request arrays are read-only views of the wire
-                # bytes; they are only read here
-                warnings.simplefilter("ignore", UserWarning)
-                x = torch.from_numpy(arr)
+        x = _as_tensor(x)
         if self.device is not None and x.dtype == torch.uint8:
             x = x.to(self.device)
         if self.resize is None and self.center_crop is None:
@@ -144,3 +153,117 @@ class ImagePreprocess:
             x, size, self.mean, self.std, crop=self.crop_window(*size),
             out_dtype=self.out_dtype, layout=self.layout,
             pixel_scale=self.pixel_scale, antialias=self.antialias)
+
+
+class RaggedImagePreprocess:
+    """N uint8 images of N different sizes -> one normalized float batch.
+
+    Called as ``pre(images, image_shapes)``: ``images`` is the flat uint8
+    ``[total_bytes]`` buffer of the images in HWC order, back to back with no
+    padding, and ``image_shapes`` the integer ``[N,2]`` rows ``(H_i, W_i)``
+    (see :func:`pack_ragged_images`). Numpy arrays or torch tensors, on CPU or
+    device; with ``device`` set the **uint8** data is moved there first and
+    one kernel launch resizes, crops and normalizes every image
+    (``ops.image_u8_ragged_resize_to_float``). ``image_shapes`` is read on
+    the host.
+
+    Every image goes through the rules of :class:`ImagePreprocess` for its
+    own size (``resize=s`` sets its shorter side to ``s``; ``center_crop``
+    starts at ``((Hr-Hc)//2, (Wr-Wc)//2)`` of its resized size), and all
+    images must end at one output size, known at construction:
+
+    * ``resize=(H, W)``, with or without ``center_crop``;
+    * ``resize=s`` (an int) with ``center_crop``;
+    * ``center_crop`` alone (each image is cropped at its own size).
+
+    Anything else raises ``ValueError`` at construction; a crop larger than
+    some image's resized size raises ``ValueError`` at call time and names
+    the image. Antialiased resizing of ragged batches is not implemented:
+    ``antialias=True`` raises ``ValueError``."""
+
+    def __init__(self, mean, std, out_dtype=None, layout: str = "nchw",
+                 pixel_scale: float = 1.0 / 255.0, device=None,
+                 resize=None, center_crop=None, antialias: bool = False):
+        if antialias:
+            raise ValueError(
+                "antialias=True is not supported for ragged image batches: "
+                "the antialiased kernels need one input size per batch")
+        self._rule = ImagePreprocess(
+            mean, std, out_dtype=out_dtype, layout=layout,
+            pixel_scale=pixel_scale, device=device, resize=resize,
+            center_crop=center_crop)
+        rule = self._rule
+        self.mean, self.std = rule.mean, rule.std
+        self.out_dtype, self.layout = rule.out_dtype, rule.layout
+        self.pixel_scale, self.device = rule.pixel_scale, rule.device
+        self.resize, self.center_crop = rule.resize, rule.center_crop
+        if self.center_crop is not None:
+            self.out_size = self.center_crop
+        elif isinstance(self.resize, tuple):
+            self.out_size = self.resize
+        else:
+            raise ValueError(
+                "RaggedImagePreprocess needs one output size for all images: "
+                "resize=(H, W), or center_crop with resize=int or alone; "
+                f"got resize={resize!r}, center_crop={center_crop!r}")
+
+    def __call__(self, images, image_shapes):
+        x = _as_tensor(images)
+        if self.device is not None and x.dtype == torch.uint8:
+            x = x.to(self.device)
+        shapes = image_shapes
+        if isinstance(shapes, torch.Tensor):
+            shapes = shapes.cpu().numpy()  # device tensor: synchronizing D2H
+        shapes = np.asarray(shapes)
+        if shapes.dtype.kind not in "iu" or shapes.ndim != 2 or \
+                shapes.shape[1] != 2:
+            raise ValueError(
+                "image_shapes must be integer [N,2] rows of (H, W), got "
+                f"dtype {shapes.dtype} shape {list(shapes.shape)}")
+        n = shapes.shape[0]
+        sizes = np.zeros((n, 2), dtype=np.int64)
+        origins = np.zeros((n, 2), dtype=np.int64)
+        for i in range(n):
+            h, w = int(shapes[i, 0]), int(shapes[i, 1])
+            if h < 1 or w < 1:
+                raise ValueError(
+                    f"image {i}: sides must be positive, got {h}x{w}")
+            size = self._rule.resized_size(h, w)
+            try:
+                window = self._rule.crop_window(*size)
+            except ValueError as e:
+                raise ValueError(f"image {i} ({h}x{w}): {e}") from None
+            sizes[i] = size
+            if window is not None:
+                origins[i] = window[:2]
+        return ops.image_u8_ragged_resize_to_float(
+            x, shapes, sizes, self.out_size, self.mean, self.std,
+            origins=origins, out_dtype=self.out_dtype, layout=self.layout,
+            pixel_scale=self.pixel_scale)
+
+
+def pack_ragged_images(images):
+    """Client side of the ragged layout: a list of ``[H_i,W_i,C]`` uint8
+    arrays -> ``(data, shapes)``, the flat uint8 ``[total_bytes]`` buffer of
+    the images back to back and the int32 ``[N,2]`` rows ``(H_i, W_i)``.
+    All images must share ``C``. Numpy only."""
+    arrays = []
+    channels = None
+    for i, img in enumerate(images):
+        arr = np.asarray(img)
+        if arr.dtype != np.uint8 or arr.ndim != 3:
+            raise ValueError(
+                f"image {i} must be a uint8 [H,W,C] array, got dtype "
+                f"{arr.dtype} shape {list(arr.shape)}")
+        if channels is None:
+            channels = arr.shape[2]
+        elif arr.shape[2] != channels:
+            raise ValueError(
+                f"image {i} has {arr.shape[2]} channels but image 0 has "
+                f"{channels}: all images of one request share C")
+        arrays.append(arr)
+    shapes = np.array([a.shape[:2] for a in arrays],
+                      dtype=np.int32).reshape(len(arrays), 2)
+    if not arrays:
+        return np.zeros((0,), dtype=np.uint8), shapes
+    return np.concatenate([a.reshape(-1) for a in arrays]), shapes

@@ -16,8 +16,10 @@ On-disk version-directory formats understood by the default loader:
   * ``model.json``          — {"family": "resnet50"|"bert_base",
                                "device": ..., "state_dict": "weights.pt"?}
                                plus optional I/O modes: "input_format"
-                               (resnet50: "float_nchw", "uint8_nhwc" or
-                               "uint8_nhwc_resize") and "antialias"
+                               (resnet50: "float_nchw", "uint8_nhwc",
+                               "uint8_nhwc_resize" or "uint8_ragged": N
+                               images of N sizes in one request) and
+                               "antialias"
                                (resnet50, with "uint8_nhwc_resize"),
                                "output_format" and "normalize_embedding"
                                (bert_base)

@@ -74,6 +74,13 @@ class Servable:
     aliases without an entry pass through untouched and the caller's dict
     is never mutated. A callable that raises ``ValueError`` is reported as
     INVALID_ARGUMENT by every transport.
+
+    A key may also be a **tuple of aliases**, for a callable that needs
+    several inputs at once (``preprocess.RaggedImagePreprocess`` takes the
+    packed pixels and their shapes): when all of them are in the request the
+    callable gets those inputs in key order, its result replaces the first
+    alias and the others are dropped before ``fn``. A request with some but
+    not all of them raises ``ValueError``.
     """
 
     def __init__(self, fn: Callable[[Dict[str, np.ndarray]], Dict[str, np.ndarray]],
@@ -89,7 +96,20 @@ class Servable:
         if self.preprocess:
             inputs = dict(inputs)
             for alias, pre in self.preprocess.items():
-                if alias in inputs:
+                if isinstance(alias, tuple):
+                    present = [a for a in alias if a in inputs]
+                    if not present:
+                        continue
+                    if len(present) != len(alias):
+                        missing = [a for a in alias if a not in inputs]
+                        raise ValueError(
+                            f"inputs {list(alias)} go together: the request "
+                            f"has {present} but not {missing}")
+                    result = pre(*(inputs[a] for a in alias))
+                    for a in alias[1:]:
+                        del inputs[a]
+                    inputs[alias[0]] = result
+                elif alias in inputs:
                     inputs[alias] = pre(inputs[alias])
         return self.fn(inputs)
 
