@@ -8,8 +8,12 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from ..preprocess import (IMAGENET_MEAN, IMAGENET_STD, ImagePreprocess,
+from ..preprocess import (IMAGENET_MEAN, IMAGENET_STD,
+                          AntialiasedRaggedImagePreprocess, ImagePreprocess,
                           RaggedImagePreprocess)
+
+_RAGGED_MODES = {"uint8_ragged": RaggedImagePreprocess,
+                 "uint8_ragged_antialias": AntialiasedRaggedImagePreprocess}
 
 
 class Bottleneck(nn.Module):
@@ -102,19 +106,29 @@ def resnet50_servable(device: str = "cpu", dtype=torch.float32,
     both). One kernel launch resizes each image's shorter side to 256, takes
     its 224x224 centre crop and normalizes
     (``RaggedImagePreprocess(resize=256, center_crop=224)``); every image
-    gets exactly what the ``uint8_nhwc_resize`` mode gives it alone.
-    ``antialias=True`` is not available in this mode."""
+    gets exactly what the ``uint8_nhwc_resize`` mode gives it alone. The
+    filter is bilinear; ``antialias=True`` is rejected in this mode, whose
+    antialiased counterpart has a name of its own:
+    ``input_format="uint8_ragged_antialias"``: the same two inputs, resized
+    with the antialiased filter in two kernel launches
+    (``AntialiasedRaggedImagePreprocess(resize=256, center_crop=224)``);
+    every image gets exactly what ``uint8_nhwc_resize`` with
+    ``antialias=True`` gives it alone. The mode name carries the filter, so
+    ``antialias=True`` on top of it is rejected like in every mode but
+    ``uint8_nhwc_resize``."""
     from ..server import Servable
 
     if input_format not in ("float_nchw", "uint8_nhwc", "uint8_nhwc_resize",
-                            "uint8_ragged"):
+                            "uint8_ragged", "uint8_ragged_antialias"):
         raise ValueError(
             f"input_format must be 'float_nchw', 'uint8_nhwc', "
-            f"'uint8_nhwc_resize' or 'uint8_ragged', got {input_format!r}")
+            f"'uint8_nhwc_resize', 'uint8_ragged' or "
+            f"'uint8_ragged_antialias', got {input_format!r}")
     if antialias and input_format == "uint8_ragged":
         raise ValueError(
             "antialias=True is not supported with input_format="
-            "'uint8_ragged': antialiased ragged batches are not implemented")
+            "'uint8_ragged': antialiased ragged batches are "
+            "input_format='uint8_ragged_antialias'")
     if antialias and input_format != "uint8_nhwc_resize":
         raise ValueError(
             "antialias=True needs input_format='uint8_nhwc_resize', got "
@@ -144,16 +158,16 @@ def resnet50_servable(device: str = "cpu", dtype=torch.float32,
             IMAGENET_MEAN, IMAGENET_STD, out_dtype=dtype, layout="nchw",
             device=device, resize=256, center_crop=224,
             antialias=bool(antialias))}
-    elif input_format == "uint8_ragged":
+    elif input_format in _RAGGED_MODES:
         images_sig = (4, [-1])                              # DT_UINT8
-        preprocess = {("images", "image_shapes"): RaggedImagePreprocess(
+        preprocess = {("images", "image_shapes"): _RAGGED_MODES[input_format](
             IMAGENET_MEAN, IMAGENET_STD, out_dtype=dtype, layout="nchw",
             device=device, resize=256, center_crop=224)}
     else:
         images_sig = (1, [-1, 3, 224, 224])                 # DT_FLOAT
         preprocess = None
     sig_inputs = {"images": images_sig}
-    if input_format == "uint8_ragged":
+    if input_format in _RAGGED_MODES:
         sig_inputs["image_shapes"] = (3, [-1, 2])           # DT_INT32
     s = Servable(
         fn,

@@ -400,11 +400,13 @@ def _first_bad(mask):
 
 def image_u8_ragged_resize_to_float(data, shapes, sizes, out_size, mean, std,
                                     origins=None, out_dtype=None,
-                                    layout="nchw", pixel_scale=1.0 / 255.0):
+                                    layout="nchw", pixel_scale=1.0 / 255.0,
+                                    *, antialias=False, _ws_cap_bytes=None):
     """Fused uint8 image ingest of a ragged batch: N images of N different
     sizes, packed back to back with no padding, are each resized, cropped to
     one shared output size and normalized into one ``[N,C,Hc,Wc]``
-    (``layout="nhwc"``: ``[N,Hc,Wc,C]``) batch, in one kernel launch.
+    (``layout="nhwc"``: ``[N,Hc,Wc,C]``) batch, in one kernel launch (two
+    with ``antialias=True``).
 
     * ``data``: contiguous 1-D uint8 torch tensor, on CPU or device. Image
       ``i`` is HWC and starts at byte ``off_i = sum_{j<i} H_j*W_j*C``.
@@ -425,13 +427,23 @@ def image_u8_ragged_resize_to_float(data, shapes, sizes, out_size, mean, std,
                       data[off_i : off_i + H_i*W_i*C].view(1,H_i,W_i,C),
                       sizes[i], mean, std,
                       crop=(top_i, left_i, Hc, Wc), out_dtype=out_dtype,
-                      layout=layout, pixel_scale=pixel_scale)[0]
+                      layout=layout, pixel_scale=pixel_scale,
+                      antialias=antialias)[0]
 
     CPU tensors run exactly this loop, so CPU-only servers work. Device
-    tensors run the gfx950 ragged kernel only (no eager fallback): the host
+    tensors run the gfx950 ragged kernels only (no eager fallback): the host
     builds a per-image table (offset, sizes, origin, ``float32(H_i/Hr_i)``,
     ``float32(W_i/Wr_i)``) and copies it on the current stream from a pinned
-    buffer. Antialiased resizing is not available for ragged batches.
+    buffer.
+
+    ``antialias=True`` (keyword only) resizes every image with the
+    antialiased triangle filter of :func:`image_u8_resize_to_float`, what PIL
+    and torchvision ``Resize`` do when they shrink a photo. On the device the
+    native entry derives each image's source-row range from the same table
+    and runs the horizontal and the vertical pass over one ragged fp32
+    workspace, two launches for the whole batch; a batch whose workspace
+    exceeds the cap runs in chunks of whole images. ``_ws_cap_bytes``
+    overrides that cap (a test hook, as on the dense op).
 
     Invalid arguments raise ``ValueError`` on both paths, before any launch,
     and name the image at fault: wrong dtype, rank or contiguity of ``data``;
@@ -523,13 +535,19 @@ def image_u8_ragged_resize_to_float(data, shapes, sizes, out_size, mean, std,
         native = require_native()
         # the kernel's per-image table, int32 [N,8]: offset (int64 as two
         # little-endian words), Hin, Win, top, left, bits of rh, bits of rw
-        table = torch.empty((N, 8), dtype=torch.int32, pin_memory=N > 0)
+        table = torch.empty((N, 8), dtype=torch.int32,
+                            pin_memory=N > 0 and not antialias)
         t = table.numpy()
         t[:, 0:2] = offsets.astype("<i8").view("<i4").reshape(N, 2)
         t[:, 2:4] = shp
         t[:, 4:6] = org
         # Python-double division rounded once to fp32, as the dense op does
         t[:, 6:8] = (shp / siz).astype(np.float32).view(np.int32)
+        if antialias:
+            # the entry reads these rows on the host and ships its own table
+            return native.u8_ragged_resize_aa_normalize(
+                data, table, C, Hc, Wc, scale, bias, out_dtype,
+                layout == "nchw", int(_ws_cap_bytes or 0))
         # pinned source: the copy is queued on the current stream and the
         # caching host allocator keeps the buffer until it has completed
         table_dev = table.to(data.device, non_blocking=True)
@@ -547,7 +565,8 @@ def image_u8_ragged_resize_to_float(data, shapes, sizes, out_size, mean, std,
             data[off:off + h * w * C].view(1, h, w, C),
             (int(siz[i, 0]), int(siz[i, 1])), mean, std,
             crop=(int(org[i, 0]), int(org[i, 1]), Hc, Wc),
-            out_dtype=out_dtype, layout=layout, pixel_scale=pixel_scale))
+            out_dtype=out_dtype, layout=layout, pixel_scale=pixel_scale,
+            antialias=antialias))
     return torch.cat(outs)
 
 

@@ -44,6 +44,13 @@ at::Tensor u8_nhwc_resize_aa_normalize(
     int64_t Hc, int64_t Wc, std::vector<double> scale,
     std::vector<double> bias, at::ScalarType out_dtype, bool out_nchw,
     int64_t ws_cap_bytes);
+at::Tensor u8_ragged_resize_aa_normalize(
+    const at::Tensor& in, const at::Tensor& table, int64_t C, int64_t Hc,
+    int64_t Wc, std::vector<double> scale, std::vector<double> bias,
+    at::ScalarType out_dtype, bool out_nchw, int64_t ws_cap_bytes);
+std::tuple<at::Tensor, at::Tensor> u8_ragged_resize_aa_plan(
+    const at::Tensor& table, int64_t in_bytes, int64_t C, int64_t Hc,
+    int64_t Wc, int64_t ws_cap_bytes);
 at::Tensor masked_mean_pool(const at::Tensor& hidden,
                             const c10::optional<at::Tensor>& mask,
                             bool normalize);
@@ -657,6 +664,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("left"), py::arg("crop_h"), py::arg("crop_w"),
         py::arg("scale"), py::arg("bias"), py::arg("out_dtype"),
         py::arg("out_nchw") = true, py::arg("ws_cap_bytes") = 0);
+  m.def("u8_ragged_resize_aa_normalize",
+        &mi355x::u8_ragged_resize_aa_normalize, py::arg("input"),
+        py::arg("table"), py::arg("channels"), py::arg("crop_h"),
+        py::arg("crop_w"), py::arg("scale"), py::arg("bias"),
+        py::arg("out_dtype"), py::arg("out_nchw") = true,
+        py::arg("ws_cap_bytes") = 0);
+  m.def("u8_ragged_resize_aa_plan", &mi355x::u8_ragged_resize_aa_plan,
+        py::arg("table"), py::arg("input_bytes"), py::arg("channels"),
+        py::arg("crop_h"), py::arg("crop_w"), py::arg("ws_cap_bytes") = 0);
   m.def("masked_mean_pool", &mi355x::masked_mean_pool, py::arg("hidden"),
         py::arg("mask") = py::none(), py::arg("normalize") = false);
   m.def("quantize_q8", &mi355x::quantize_q8, py::arg("input"),

@@ -12,7 +12,8 @@ selects the antialiased resize kernels for downscaled photos.
 ``RaggedImagePreprocess`` is the mixed-size case: one request carries N
 images of N different sizes packed back to back (``pack_ragged_images``) and
 one kernel launch (``ops.image_u8_ragged_resize_to_float``) turns them into
-one batch.
+one batch; ``AntialiasedRaggedImagePreprocess`` does the same with the
+antialiased filter, in two launches.
 """
 from __future__ import annotations
 
@@ -178,16 +179,20 @@ class RaggedImagePreprocess:
 
     Anything else raises ``ValueError`` at construction; a crop larger than
     some image's resized size raises ``ValueError`` at call time and names
-    the image. Antialiased resizing of ragged batches is not implemented:
-    ``antialias=True`` raises ``ValueError``."""
+    the image. This class resizes with the 2-tap bilinear filter
+    (``pre.antialias`` is ``False``) and ``antialias=True`` raises
+    ``ValueError``: the antialiased filter is
+    :class:`AntialiasedRaggedImagePreprocess`."""
+
+    antialias = False
 
     def __init__(self, mean, std, out_dtype=None, layout: str = "nchw",
                  pixel_scale: float = 1.0 / 255.0, device=None,
                  resize=None, center_crop=None, antialias: bool = False):
         if antialias:
             raise ValueError(
-                "antialias=True is not supported for ragged image batches: "
-                "the antialiased kernels need one input size per batch")
+                "RaggedImagePreprocess is bilinear and takes no "
+                "antialias=True: use AntialiasedRaggedImagePreprocess")
         self._rule = ImagePreprocess(
             mean, std, out_dtype=out_dtype, layout=layout,
             pixel_scale=pixel_scale, device=device, resize=resize,
@@ -239,7 +244,24 @@ class RaggedImagePreprocess:
         return ops.image_u8_ragged_resize_to_float(
             x, shapes, sizes, self.out_size, self.mean, self.std,
             origins=origins, out_dtype=self.out_dtype, layout=self.layout,
-            pixel_scale=self.pixel_scale)
+            pixel_scale=self.pixel_scale, antialias=self.antialias)
+
+
+class AntialiasedRaggedImagePreprocess(RaggedImagePreprocess):
+    """:class:`RaggedImagePreprocess` with the antialiased triangle filter
+    (``ImagePreprocess(..., antialias=True)`` per image; what PIL and
+    torchvision ``Resize`` do when they shrink a photo): the same call, the
+    same construction rules without the ``antialias`` parameter, and two
+    kernel launches for the batch. ``pre.antialias`` is ``True``."""
+
+    antialias = True
+
+    def __init__(self, mean, std, out_dtype=None, layout: str = "nchw",
+                 pixel_scale: float = 1.0 / 255.0, device=None,
+                 resize=None, center_crop=None):
+        super().__init__(mean, std, out_dtype=out_dtype, layout=layout,
+                         pixel_scale=pixel_scale, device=device,
+                         resize=resize, center_crop=center_crop)
 
 
 def pack_ragged_images(images):

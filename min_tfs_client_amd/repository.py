@@ -17,9 +17,10 @@ On-disk version-directory formats understood by the default loader:
                                "device": ..., "state_dict": "weights.pt"?}
                                plus optional I/O modes: "input_format"
                                (resnet50: "float_nchw", "uint8_nhwc",
-                               "uint8_nhwc_resize" or "uint8_ragged": N
-                               images of N sizes in one request) and
-                               "antialias"
+                               "uint8_nhwc_resize", "uint8_ragged": N
+                               images of N sizes in one request, or
+                               "uint8_ragged_antialias": the same with the
+                               antialiased filter) and "antialias"
                                (resnet50, with "uint8_nhwc_resize"),
                                "output_format" and "normalize_embedding"
                                (bert_base)

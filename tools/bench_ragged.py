@@ -4,6 +4,7 @@ per-image loop of dense calls they replace, one GPU.
 
     python tools/bench_ragged.py             # op timings, JSON lines
     python tools/bench_ragged.py --predict   # + ResNet-50 Predict comparison
+    python tools/bench_ragged.py --antialias # op timings, antialiased filter
 
 The parent process never touches the GPU. Every step (one N of the op
 timings, the Predict comparison) runs in a fresh child process under its own
@@ -30,6 +31,14 @@ Op timings, u8 -> bf16 NCHW, short side 256 then the 224 centre crop, N in
 warm-up then interleaved rounds in one process; the median round is reported
 with the range over rounds. ``host_us`` is the host clock per ``ragged``
 call without a device wait (what the calling thread spends).
+
+``--antialias`` times the same set with ``antialias=True`` everywhere (rows
+are tagged ``"antialias": true``): ``ragged`` is the whole antialiased op,
+``ragged_kernel`` the native entry on a pre-built HOST table (the entry
+derives the row ranges and ships its own device table, so that work is
+inside the number), ``loop`` the N dense antialiased calls plus ``torch.cat``
+the op replaces, ``dense`` the dense antialiased kernels on N images of one
+size.
 
 ``--predict``: ``resnet50_servable("cuda:0", bf16)`` on one raw-Predict
 server on a unix socket, one ``TurboPredictClient``, host tensors in and
@@ -92,7 +101,7 @@ def _stats(values):
     return {"median": v[len(v) // 2], "min": v[0], "max": v[-1]}
 
 
-def run_op_case(n):
+def run_op_case(n, antialias=False):
     import numpy as np
     import torch
 
@@ -129,7 +138,7 @@ def run_op_case(n):
     def ragged(s=shapes_np):
         return ops.image_u8_ragged_resize_to_float(
             flat, s, sizes, (224, 224), IMAGENET_MEAN, IMAGENET_STD,
-            origins=origins, out_dtype=dtype)
+            origins=origins, out_dtype=dtype, antialias=antialias)
 
     # the table exactly as the op builds it, kept on the device
     offsets = np.zeros(n, dtype=np.int64)
@@ -141,9 +150,13 @@ def run_op_case(n):
     t[:, 4:6] = origins
     t[:, 6:8] = (shapes_np.astype(np.int64) / sizes).astype(
         np.float32).view(np.int32)
-    table_dev = torch.from_numpy(t).to(dev)
+    table_host = torch.from_numpy(t)
+    table_dev = table_host.to(dev)
 
     def ragged_kernel():
+        if antialias:
+            return native.u8_ragged_resize_aa_normalize(
+                flat, table_host, 3, 224, 224, scale, bias, dtype, True)
         return native.u8_ragged_resize_normalize(
             flat, table_dev, 3, 224, 224, scale, bias, dtype, True)
 
@@ -151,19 +164,21 @@ def run_op_case(n):
         return torch.cat([ops.image_u8_resize_to_float(
             x, tuple(int(v) for v in sizes[i]), IMAGENET_MEAN, IMAGENET_STD,
             crop=(int(origins[i][0]), int(origins[i][1]), 224, 224),
-            out_dtype=dtype) for i, x in enumerate(batched)])
+            out_dtype=dtype, antialias=antialias)
+            for i, x in enumerate(batched)])
 
     def dense():
         return ops.image_u8_resize_to_float(
             same_x, tuple(int(v) for v in same_sizes[0]), IMAGENET_MEAN,
             IMAGENET_STD,
             crop=(int(same_origins[0][0]), int(same_origins[0][1]), 224, 224),
-            out_dtype=dtype)
+            out_dtype=dtype, antialias=antialias)
 
     def ragged_same():
         return ops.image_u8_ragged_resize_to_float(
             same_flat, same_np, same_sizes, (224, 224), IMAGENET_MEAN,
-            IMAGENET_STD, origins=same_origins, out_dtype=dtype)
+            IMAGENET_STD, origins=same_origins, out_dtype=dtype,
+            antialias=antialias)
 
     assert torch.equal(ragged(), loop())
     assert torch.equal(ragged(), ragged_kernel())
@@ -179,7 +194,8 @@ def run_op_case(n):
         for k, fn in fns.items():
             rounds[k].append(time_kernel(fn, reps, 10))
         host.append(time_host(ragged, reps))
-    row = {"case": f"n{n}", "images": n, "input_bytes": flat.numel(),
+    row = {"case": f"n{n}", "antialias": antialias, "images": n,
+           "input_bytes": flat.numel(),
            "out": "bfloat16", "crop": 224,
            "shapes": shapes if n <= 4 else shapes[:4] + ["..."]}
     for k, v in rounds.items():
@@ -276,18 +292,22 @@ def main():
                     help="also compare one ragged Predict of 32 images with "
                          "32 single-image Predicts")
     ap.add_argument("--only-predict", action="store_true")
+    ap.add_argument("--antialias", action="store_true",
+                    help="time the antialiased ragged op against the loop of "
+                         "dense antialiased calls and the dense kernels")
     ap.add_argument("--op-case", type=int, choices=OP_NS,
                     help="(child) run the op timings at this N")
     ap.add_argument("--predict-child", action="store_true",
                     help="(child) run the Predict comparison")
     a = ap.parse_args()
     if a.op_case:
-        return run_op_case(a.op_case)
+        return run_op_case(a.op_case, a.antialias)
     if a.predict_child:
         return run_predict()
     if not a.only_predict:
         for n in OP_NS:
-            run_step(["--op-case", str(n)])
+            run_step(["--op-case", str(n)] +
+                     (["--antialias"] if a.antialias else []))
     if a.predict or a.only_predict:
         run_step(["--predict-child"])
 
