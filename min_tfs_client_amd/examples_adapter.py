@@ -19,6 +19,8 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
+from . import ops
+from .postprocess import TopKClassification
 from .server import Servable
 from .wire import messages as pb
 
@@ -124,14 +126,50 @@ def examples_to_feature_arrays(input_proto) -> Dict[str, np.ndarray]:
 class ClassificationAdapter(Servable):
     """Makes a tensor servable classify tf.Examples: features are
     extracted, the inner servable runs, and ``scores_output`` (shape
-    [batch, n_classes]) becomes Classifications with optional labels."""
+    [batch, n_classes]) becomes Classifications with optional labels.
+
+    ``top_k=None`` (default) reports every class in index order with the
+    value of ``scores_output`` as it is. With ``top_k`` set (1..64),
+    ``scores_output`` is taken as logits and goes through
+    ``ops.softmax_topk`` on the device it lives on: each Classifications
+    holds exactly ``top_k`` classes in rank order, each with its label and
+    its softmax probability."""
 
     def __init__(self, inner: Servable, scores_output: str = "scores",
-                 labels: Optional[List[str]] = None):
+                 labels: Optional[List[str]] = None,
+                 top_k: Optional[int] = None):
         super().__init__(inner.fn, inner.signature, inner.signature_name)
         self.inner = inner
         self.scores_output = scores_output
         self.labels = labels
+        if top_k is not None:
+            # validates the range at construction, not on the first request
+            top_k = TopKClassification(top_k).k
+        self.top_k = top_k
+
+    def _label(self, j: int) -> str:
+        return (self.labels[j] if self.labels and j < len(self.labels)
+                else str(j))
+
+    def _classify_top_k(self, logits) -> "pb.ClassificationResult":
+        import torch
+
+        if not isinstance(logits, torch.Tensor):
+            logits = torch.as_tensor(np.asarray(logits))
+        if logits.dim() == 1:
+            logits = logits[:, None]
+        if logits.dtype not in (torch.float32, torch.bfloat16,
+                                torch.float16):
+            logits = logits.float()    # e.g. float64 from a numpy model
+        scores, classes = ops.softmax_topk(logits.contiguous(), self.top_k)
+        result = pb.ClassificationResult()
+        for srow, crow in zip(scores.tolist(), classes.tolist()):
+            cls = result.classifications.add()
+            for s, j in zip(srow, crow):
+                c = cls.classes.add()
+                c.label = self._label(j)
+                c.score = s
+        return result
 
     def classify(self, input_proto) -> "pb.ClassificationResult":
         features = examples_to_feature_arrays(input_proto)
@@ -141,6 +179,8 @@ class ClassificationAdapter(Servable):
                 f"Expected classification scores output "
                 f"{self.scores_output!r}; servable returned "
                 f"{sorted(outputs)}")
+        if self.top_k is not None:
+            return self._classify_top_k(outputs[self.scores_output])
         scores = np.asarray(outputs[self.scores_output])
         if scores.ndim == 1:
             scores = scores[:, None]

@@ -82,7 +82,8 @@ def resnet50(num_classes: int = 1000) -> ResNet:
 
 def resnet50_servable(device: str = "cpu", dtype=torch.float32,
                       seed: int = 0, input_format: str = "float_nchw",
-                      antialias: bool = False):
+                      antialias: bool = False, output_format: str = "logits",
+                      top_k: int = 5):
     """ResNet-50 Servable: input alias "images", output "logits" (N,1000).
 
     ``input_format="float_nchw"`` (default): "images" is DT_FLOAT
@@ -115,7 +116,18 @@ def resnet50_servable(device: str = "cpu", dtype=torch.float32,
     every image gets exactly what ``uint8_nhwc_resize`` with
     ``antialias=True`` gives it alone. The mode name carries the filter, so
     ``antialias=True`` on top of it is rejected like in every mode but
-    ``uint8_nhwc_resize``."""
+    ``uint8_nhwc_resize``.
+
+    ``output_format="logits"`` (default): the only output is "logits",
+    DT_FLOAT (N,1000).
+    ``output_format="topk"``: the outputs are "scores", DT_FLOAT (N,top_k),
+    and "classes", DT_INT32 (N,top_k) — the ``top_k`` (1..64, default 5) most
+    probable classes of each image in rank order with their softmax
+    probabilities, 40 bytes per image at 5 instead of 4000. The head runs on the
+    server in one fused kernel (``postprocess.TopKClassification``,
+    ``ops.softmax_topk``) straight from the model's own dtype; the full
+    logits never leave the device."""
+    from ..postprocess import TopKClassification
     from ..server import Servable
 
     if input_format not in ("float_nchw", "uint8_nhwc", "uint8_nhwc_resize",
@@ -133,6 +145,13 @@ def resnet50_servable(device: str = "cpu", dtype=torch.float32,
         raise ValueError(
             "antialias=True needs input_format='uint8_nhwc_resize', got "
             f"{input_format!r}")
+    if output_format not in ("logits", "topk"):
+        raise ValueError(
+            f"output_format must be 'logits' or 'topk', got "
+            f"{output_format!r}")
+    topk = output_format == "topk"
+    # top_k is validated in every mode: a typo must not wait for "topk"
+    postprocess = TopKClassification(top_k)
 
     torch.manual_seed(seed)
     model = resnet50().to(device=device, dtype=dtype).eval()
@@ -145,7 +164,9 @@ def resnet50_servable(device: str = "cpu", dtype=torch.float32,
         # a no-op (same tensor) when preprocessing already produced
         # device/dtype
         x = x.to(device=device, dtype=dtype)
-        return {"logits": s.module(x).float()}
+        logits = s.module(x)
+        # the top-k head reads the model's own dtype
+        return {"logits": logits if topk else logits.float()}
 
     if input_format == "uint8_nhwc":
         images_sig = (4, [-1, 224, 224, 3])                 # DT_UINT8
@@ -169,13 +190,19 @@ def resnet50_servable(device: str = "cpu", dtype=torch.float32,
     sig_inputs = {"images": images_sig}
     if input_format in _RAGGED_MODES:
         sig_inputs["image_shapes"] = (3, [-1, 2])           # DT_INT32
+    if topk:
+        outputs = {"scores": (1, [-1, postprocess.k]),      # DT_FLOAT
+                   "classes": (3, [-1, postprocess.k])}     # DT_INT32
+    else:
+        outputs = {"logits": (1, [-1, 1000])}
     s = Servable(
         fn,
         signature={
             "method_name": "tensorflow/serving/predict",
             "inputs": sig_inputs,
-            "outputs": {"logits": (1, [-1, 1000])},
+            "outputs": outputs,
         },
-        preprocess=preprocess)
+        preprocess=preprocess,
+        postprocess=postprocess if topk else None)
     s.module = model
     return s

@@ -8,6 +8,7 @@ to eager PyTorch, so a passing GPU test means the HIP path actually ran.
 from __future__ import annotations
 
 import functools
+import operator
 from typing import Optional
 
 try:
@@ -635,6 +636,70 @@ def masked_mean_pool(hidden, mask=None, normalize=False):
     if normalize:
         y = y / y.norm(dim=1, keepdim=True).clamp(min=1e-12)
     return y.contiguous()
+
+
+SOFTMAX_TOPK_MAX_K = 64
+
+
+def softmax_topk(logits, k):
+    """Fused classification head: ``[B,C]`` logits (f32, bf16 or f16,
+    contiguous) -> ``(scores, classes)``, fp32 ``[B,k]`` and int32 ``[B,k]``,
+    the ``k`` most probable classes of every row in rank order.
+    ``1 <= k <= min(C, 64)``.
+
+    The order is exact: by ``float(logit)`` descending, equal values lower
+    index first, ``-0.0`` equal to ``+0.0``, NaN above ``+Inf`` (NaNs among
+    themselves by index) — ``torch.sort(x.float(), 1, descending=True,
+    stable=True)`` truncated to ``k``.
+
+        m       = the rank-0 logit
+        score_j = exp(x_j - m) / sum_i exp(x_i - m)
+
+    in fp32 with an IEEE divide. A row holding NaN or ``+Inf`` has NaN
+    scores (its classes are still ranked), ``-Inf`` logits score exactly 0
+    and rank last. The result is deterministic: the same input gives
+    bit-identical output on every run.
+
+    Device tensors run the gfx950 kernel (one workgroup per row, the row is
+    read once and kept on chip up to 8192 classes; no eager fallback); CPU
+    tensors use an eager expression with the same semantics, so CPU-only
+    servers work too. ``B == 0`` returns empty tensors. Invalid arguments
+    raise ``ValueError`` on both paths."""
+    if not isinstance(logits, torch.Tensor):
+        raise ValueError("softmax_topk expects a torch tensor")
+    if logits.dim() != 2:
+        raise ValueError(
+            f"softmax_topk expects [B,C], got rank {logits.dim()}")
+    if logits.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError(
+            "softmax_topk expects float32, bfloat16 or float16, got "
+            f"{logits.dtype}")
+    if not logits.is_contiguous():
+        raise ValueError("softmax_topk expects a contiguous tensor")
+    B, C = (int(d) for d in logits.shape)
+    try:
+        if isinstance(k, bool):
+            raise TypeError
+        k = operator.index(k)
+    except TypeError:
+        raise ValueError(f"k must be an integer, got {k!r}") from None
+    if not 1 <= k <= min(C, SOFTMAX_TOPK_MAX_K):
+        raise ValueError(
+            f"k must be in 1..min(C, {SOFTMAX_TOPK_MAX_K}), got {k} with "
+            f"C = {C}")
+    if B == 0:
+        return (torch.empty((0, k), dtype=torch.float32,
+                            device=logits.device),
+                torch.empty((0, k), dtype=torch.int32, device=logits.device))
+    if logits.is_cuda:
+        scores, classes = require_native().softmax_topk(logits, k)
+        return scores, classes
+    x = logits.float()
+    order = torch.sort(x, dim=1, descending=True,
+                       stable=True).indices[:, :k]
+    e = torch.exp(x - x.gather(1, order[:, :1]))
+    scores = e.gather(1, order) / e.sum(1, keepdim=True)
+    return scores.contiguous(), order.to(torch.int32).contiguous()
 
 
 def pack_tensor_proto(tensor):

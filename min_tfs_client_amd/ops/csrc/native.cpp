@@ -54,6 +54,8 @@ std::tuple<at::Tensor, at::Tensor> u8_ragged_resize_aa_plan(
 at::Tensor masked_mean_pool(const at::Tensor& hidden,
                             const c10::optional<at::Tensor>& mask,
                             bool normalize);
+std::tuple<at::Tensor, at::Tensor> softmax_topk(const at::Tensor& logits,
+                                                int64_t k);
 at::Tensor quantize_q8(const at::Tensor& in, double scale, double zp);
 at::Tensor dequantize_q8(const at::Tensor& in, double scale, double zp);
 void copy_device_to_host_ptr(const at::Tensor& src, void* dst, size_t n,
@@ -675,6 +677,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("crop_h"), py::arg("crop_w"), py::arg("ws_cap_bytes") = 0);
   m.def("masked_mean_pool", &mi355x::masked_mean_pool, py::arg("hidden"),
         py::arg("mask") = py::none(), py::arg("normalize") = false);
+  m.def("softmax_topk", &mi355x::softmax_topk, py::arg("logits"),
+        py::arg("k"));
   m.def("quantize_q8", &mi355x::quantize_q8, py::arg("input"),
         py::arg("scale"), py::arg("zero_point") = 0.0);
   m.def("dequantize_q8", &mi355x::dequantize_q8, py::arg("input"),

@@ -37,6 +37,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <limits>
 #include <mutex>
 #include <stdexcept>
 #include <tuple>
@@ -1422,6 +1423,161 @@ __global__ void __launch_bounds__(kPoolBlock) masked_pool_finalize_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// fused softmax + top-k classification head: [B,C] -> scores, classes [B,k]
+// ---------------------------------------------------------------------------
+// Order (exact, integer only): rank by float(logit) descending, equal values
+// lower index first, -0.0 == +0.0, NaN above +Inf and NaNs among themselves
+// by index: torch.sort(x.float(), 1, descending=True, stable=True)[:, :k].
+// Every element gets a unique 64-bit key
+//   key32  = monotone map of the fp32 bits (sign set: ~u, else u | 1<<31)
+//            after -0.0 -> +0.0 and any NaN -> 0x7FC00000 (key 0xFFC00000,
+//            above +Inf's 0xFF800000)
+//   packed = (key32 << 32) | ~index
+// so a larger packed key is an earlier rank. The smallest packed key (-Inf)
+// is above 0 and the largest (NaN at index 0) is below ~0, which serve as
+// "nothing found" and "no bound yet".
+//
+// Scores: m = the rank-0 logit (read back at the selected index, not an
+// fmaxf), score_j = expf(x_j - m) / sum_i expf(x_i - m) in fp32 with an IEEE
+// divide (`__fdiv_rn`). A row holding NaN or +Inf therefore gets NaN scores
+// (m is NaN, or Inf - Inf is), a row of only -Inf too, and a -Inf logit
+// under a finite maximum scores exactly 0 and ranks last.
+//
+// One 256-thread workgroup per row:
+//  1. load: the row is read once from global memory, converted to fp32 and
+//     staged in LDS when C <= kTopkLdsFloats (8192, 32 KB static). Longer
+//     rows are not staged; the later passes re-read them from global memory
+//     (L2-resident: the workgroup has just read them).
+//  2. select: k rounds. In round j every thread takes the maximum packed key
+//     of its elements that is strictly below round j-1's winner; a fixed
+//     shuffle tree per wave and LDS across the 4 waves give the block-wide
+//     winner. Keys are unique, so no "taken" marks are needed and k <= C
+//     rounds always find one.
+//  3. sum: one more pass adds expf(x_i - m) per thread in element order,
+//     then the same fixed tree (pool_block_sum). The order depends only on
+//     (C, path), so the output is bit-identical from run to run.
+//  4. threads j < k write classes[j] and scores[j].
+//
+// Paths and thresholds (the tests pin one shape on each side):
+//  * vector path: VEC = 16/sizeof(T) elements per lane per load (4 f32,
+//    8 bf16/f16), taken iff the base pointer and C*sizeof(T) are multiples of
+//    16 (then every row base is, and C % VEC == 0); otherwise scalar loads.
+//    Staged rows are walked element-strided (thread t: t, t+256, ...) in
+//    passes 2-3 whatever the load path; re-read rows are walked the way they
+//    are loaded.
+//  * C <= 8192 staged in LDS, C >= 8193 re-read.
+//  * grid: min(B, 2048) workgroups (grid_for), grid-stride over rows.
+//  * 1 <= k <= min(C, 64); B == 0 returns without launching.
+constexpr int kTopkBlock = 256;          // 4 waves, as pool_block_sum expects
+constexpr int kTopkMaxK = 64;
+constexpr int kTopkLdsFloats = 8192;     // 32 KB
+static_assert(kTopkBlock == kPoolBlock, "pool_block_sum is shared");
+static_assert(kTopkMaxK <= kTopkBlock, "one thread writes one rank");
+
+__device__ __forceinline__ uint64_t topk_pack(float x, uint32_t index) {
+  uint32_t u = __float_as_uint(x);
+  if ((u & 0x7FFFFFFFu) > 0x7F800000u) u = 0x7FC00000u;  // any NaN
+  else if (u == 0x80000000u) u = 0u;                     // -0.0
+  const uint32_t key = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return (uint64_t(key) << 32) | uint64_t(~index);
+}
+
+// Maximum of `v` over the workgroup, the same value in every thread.
+__device__ __forceinline__ uint64_t topk_block_max(uint64_t v, uint64_t* red) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const uint32_t hi = __shfl_down(uint32_t(v >> 32), off, 64);
+    const uint32_t lo = __shfl_down(uint32_t(v), off, 64);
+    const uint64_t o = (uint64_t(hi) << 32) | lo;
+    v = o > v ? o : v;
+  }
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  __syncthreads();  // red may still be read from the previous round
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  uint64_t best = red[0];
+#pragma unroll
+  for (int w = 1; w < kPoolWaves; ++w) best = red[w] > best ? red[w] : best;
+  return best;
+}
+
+// f(index, float value) for this thread's share of a row in global memory.
+template <typename CVT, int VEC, typename F>
+__device__ __forceinline__ void topk_for_each_global(
+    const typename CVT::In* __restrict__ row, int C, F&& f) {
+  for (int v = threadIdx.x; v < C / VEC; v += kTopkBlock) {
+    typename CVT::In raw[VEC];
+    pool_load<CVT, VEC>(row + int64_t(v) * VEC, raw);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) f(v * VEC + e, CVT::cvt(raw[e]));
+  }
+}
+
+// f(index, float value) for this thread's share of the row, staged or not.
+template <typename CVT, int VEC, bool STAGED, typename F>
+__device__ __forceinline__ void topk_for_each(
+    const typename CVT::In* __restrict__ row, const float* stage, int C,
+    F&& f) {
+  if constexpr (STAGED) {
+    for (int i = threadIdx.x; i < C; i += kTopkBlock) f(i, stage[i]);
+  } else {
+    topk_for_each_global<CVT, VEC>(row, C, f);
+  }
+}
+
+template <typename CVT, int VEC, bool STAGED>
+__global__ void __launch_bounds__(kTopkBlock) softmax_topk_kernel(
+    const typename CVT::In* __restrict__ logits, float* __restrict__ scores,
+    int32_t* __restrict__ classes, int64_t B, int C, int k) {
+  __shared__ __attribute__((aligned(16)))
+      float stage[STAGED ? kTopkLdsFloats : 1];
+  __shared__ uint64_t win[kTopkMaxK];
+  __shared__ uint64_t red_max[kPoolWaves];
+  __shared__ float red_sum[kPoolWaves];
+  for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
+    const typename CVT::In* row = logits + b * C;
+    if constexpr (STAGED) {
+      // the previous row's readers of `stage` and `win` are done
+      __syncthreads();
+      topk_for_each_global<CVT, VEC>(
+          row, C, [&](int i, float x) { stage[i] = x; });
+      __syncthreads();
+    }
+    auto value_at = [&](uint32_t i) -> float {
+      if constexpr (STAGED) return stage[i];
+      else return CVT::cvt(row[i]);
+    };
+
+    uint64_t prev = ~uint64_t(0), first = 0;
+    for (int j = 0; j < k; ++j) {
+      uint64_t best = 0;
+      topk_for_each<CVT, VEC, STAGED>(row, stage, C, [&](int i, float x) {
+        const uint64_t c = topk_pack(x, uint32_t(i));
+        if (c < prev && c > best) best = c;
+      });
+      prev = topk_block_max(best, red_max);
+      if (j == 0) first = prev;
+      // win[j] of the previous row was last read before this round's
+      // barriers; this row's readers wait for those of pool_block_sum
+      if (threadIdx.x == 0) win[j] = prev;
+    }
+
+    const float m = value_at(~uint32_t(first));
+    float part = 0.f;
+    topk_for_each<CVT, VEC, STAGED>(row, stage, C, [&](int, float x) {
+      part += expf(x - m);
+    });
+    const float total = pool_block_sum(part, red_sum);
+    if (int(threadIdx.x) < k) {
+      const uint32_t idx = ~uint32_t(win[threadIdx.x]);
+      scores[b * k + threadIdx.x] = __fdiv_rn(expf(value_at(idx) - m), total);
+      classes[b * k + threadIdx.x] = int32_t(idx);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // launch helpers
 // ---------------------------------------------------------------------------
 
@@ -2327,6 +2483,59 @@ at::Tensor masked_mean_pool(const at::Tensor& hidden,
   else by_vec(F16ToF32{});
   HIP_CHECK(hipGetLastError());
   return out;
+}
+
+// Fused softmax + top-k of [B,C] logits: fp32 scores [B,k] and int32 classes
+// [B,k] in rank order; see the kernel section for the order, the score
+// formula, paths and thresholds.
+std::tuple<at::Tensor, at::Tensor> softmax_topk(const at::Tensor& logits,
+                                                int64_t k) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.is_contiguous(),
+              "softmax_topk expects a contiguous device tensor [B,C]");
+  const auto id = logits.scalar_type();
+  TORCH_CHECK(id == at::kFloat || id == at::kBFloat16 || id == at::kHalf,
+              "softmax_topk: logits must be f32, bf16 or f16");
+  const int64_t B = logits.size(0), C = logits.size(1);
+  TORCH_CHECK(C <= std::numeric_limits<int32_t>::max(),
+              "softmax_topk: classes are int32, C is ", C);
+  TORCH_CHECK(k >= 1 && k <= std::min<int64_t>(C, kTopkMaxK),
+              "softmax_topk: k must be in 1..min(C, ", kTopkMaxK, "), got ", k,
+              " with C = ", C);
+  auto scores = at::empty({B, k}, logits.options().dtype(at::kFloat));
+  auto classes = at::empty({B, k}, logits.options().dtype(at::kInt));
+  if (B == 0) return {scores, classes};  // zero grid: never launch
+
+  const bool vec =
+      (reinterpret_cast<uintptr_t>(logits.const_data_ptr()) & 15) == 0 &&
+      (C * logits.element_size()) % 16 == 0;
+  const bool staged = C <= kTopkLdsFloats;
+  const int grid = grid_for(B * kTopkBlock, kTopkBlock);
+  auto launch = [&](auto cvt_tag, auto vec_tag, auto staged_tag) {
+    using CVT = decltype(cvt_tag);
+    hipLaunchKernelGGL(
+        (softmax_topk_kernel<CVT, decltype(vec_tag)::value,
+                             decltype(staged_tag)::value>),
+        dim3(grid), dim3(kTopkBlock), 0, current_stream(),
+        reinterpret_cast<const typename CVT::In*>(logits.const_data_ptr()),
+        scores.data_ptr<float>(), classes.data_ptr<int32_t>(), B, int(C),
+        int(k));
+  };
+  auto by_staged = [&](auto cvt_tag, auto vec_tag) {
+    if (staged) launch(cvt_tag, vec_tag, std::true_type{});
+    else launch(cvt_tag, vec_tag, std::false_type{});
+  };
+  auto by_vec = [&](auto cvt_tag) {
+    using In = typename decltype(cvt_tag)::In;
+    if (vec)
+      by_staged(cvt_tag, std::integral_constant<int, 16 / int(sizeof(In))>{});
+    else
+      by_staged(cvt_tag, std::integral_constant<int, 1>{});
+  };
+  if (id == at::kFloat) by_vec(IdF32{});
+  else if (id == at::kBFloat16) by_vec(Bf16ToF32{});
+  else by_vec(F16ToF32{});
+  HIP_CHECK(hipGetLastError());
+  return {scores, classes};
 }
 
 at::Tensor quantize_q8(const at::Tensor& in, double scale,

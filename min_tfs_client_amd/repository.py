@@ -22,8 +22,11 @@ On-disk version-directory formats understood by the default loader:
                                "uint8_ragged_antialias": the same with the
                                antialiased filter) and "antialias"
                                (resnet50, with "uint8_nhwc_resize"),
-                               "output_format" and "normalize_embedding"
-                               (bert_base)
+                               "output_format" (resnet50: "logits" or
+                               "topk"; bert_base: "hidden" or
+                               "sentence_embedding"), "top_k" (resnet50,
+                               with "topk": 1..64 classes per image) and
+                               "normalize_embedding" (bert_base)
   * ``model.pt``            — TorchScript module (torch.jit.load)
 plus TF-style ``assets.extra/tf_serving_warmup_requests`` (a TFRecord of
 serialized PredictionLog protos — framing per TF's RecordWriter: length,
@@ -172,7 +175,9 @@ def default_loader(name: str, version_dir: str,
         # present; an unknown value is the factory's ValueError
         if family == "resnet50":
             from .models import resnet50_servable
-            modes = {k: cfg[k] for k in ("input_format", "antialias")
+            modes = {k: cfg[k]
+                     for k in ("input_format", "antialias", "output_format",
+                               "top_k")
                      if k in cfg}
             servable = resnet50_servable(device, **modes)
         elif family == "bert_base":

@@ -81,16 +81,27 @@ class Servable:
     callable gets those inputs in key order, its result replaces the first
     alias and the others are dropped before ``fn``. A request with some but
     not all of them raises ``ValueError``.
+
+    ``postprocess`` is the output-side counterpart: an optional callable
+    ``{alias: tensor} -> {alias: tensor}`` applied to the whole result of
+    ``fn`` (see ``postprocess.py``); what it returns is the response, so
+    ``signature["outputs"]`` describes its outputs. A ``ValueError`` from it
+    is INVALID_ARGUMENT as well.
     """
 
     def __init__(self, fn: Callable[[Dict[str, np.ndarray]], Dict[str, np.ndarray]],
                  signature: Optional[dict] = None,
                  signature_name: str = "serving_default",
-                 preprocess: Optional[Dict[str, Callable]] = None):
+                 preprocess: Optional[Dict[str, Callable]] = None,
+                 postprocess: Optional[Callable[[dict], dict]] = None):
+        if postprocess is not None and not callable(postprocess):
+            raise ValueError(
+                f"postprocess must be callable, got {postprocess!r}")
         self.fn = fn
         self.signature = signature or {}
         self.signature_name = signature_name
         self.preprocess = dict(preprocess) if preprocess else {}
+        self.postprocess = postprocess
 
     def __call__(self, inputs: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
         if self.preprocess:
@@ -111,7 +122,10 @@ class Servable:
                     inputs[alias[0]] = result
                 elif alias in inputs:
                     inputs[alias] = pre(inputs[alias])
-        return self.fn(inputs)
+        outputs = self.fn(inputs)
+        if self.postprocess is not None:
+            outputs = self.postprocess(outputs)
+        return outputs
 
 
 def identity_servable() -> Servable:
