@@ -10,10 +10,11 @@ import torch.nn as nn
 
 from ..preprocess import (IMAGENET_MEAN, IMAGENET_STD,
                           AntialiasedRaggedImagePreprocess, ImagePreprocess,
-                          RaggedImagePreprocess)
+                          RaggedImagePreprocess, Yuv420ImagePreprocess)
 
 _RAGGED_MODES = {"uint8_ragged": RaggedImagePreprocess,
                  "uint8_ragged_antialias": AntialiasedRaggedImagePreprocess}
+_YUV_MODES = {"nv12_resize": "nv12", "i420_resize": "i420"}
 
 
 class Bottleneck(nn.Module):
@@ -83,7 +84,7 @@ def resnet50(num_classes: int = 1000) -> ResNet:
 def resnet50_servable(device: str = "cpu", dtype=torch.float32,
                       seed: int = 0, input_format: str = "float_nchw",
                       antialias: bool = False, output_format: str = "logits",
-                      top_k: int = 5):
+                      top_k: int = 5, yuv_matrix: str = "bt601"):
     """ResNet-50 Servable: input alias "images", output "logits" (N,1000).
 
     ``input_format="float_nchw"`` (default): "images" is DT_FLOAT
@@ -117,6 +118,17 @@ def resnet50_servable(device: str = "cpu", dtype=torch.float32,
     ``antialias=True`` gives it alone. The mode name carries the filter, so
     ``antialias=True`` on top of it is rejected like in every mode but
     ``uint8_nhwc_resize``.
+    ``input_format="nv12_resize"`` / ``"i420_resize"``: "images" is DT_UINT8
+    (N,H*3/2,W), YUV 4:2:0 frames of any even size as a video or JPEG decoder
+    emits them (NV12: interleaved chroma, I420: planar), 1.5 bytes per pixel,
+    half the request bytes of ``uint8_nhwc_resize``. One kernel launch
+    converts to RGB with the integer matrix ``yuv_matrix`` ("bt601", the
+    default, "bt709" or "bt601_full"), resizes the shorter side to 256, takes
+    the 224x224 centre crop and normalizes
+    (``Yuv420ImagePreprocess(resize=256, center_crop=224)``): exactly what
+    ``uint8_nhwc_resize`` gives for the converted RGB frames
+    (``ops.yuv420_to_rgb_u8``). The filter is bilinear; ``antialias=True`` is
+    rejected, and so is a non-default ``yuv_matrix`` in every other mode.
 
     ``output_format="logits"`` (default): the only output is "logits",
     DT_FLOAT (N,1000).
@@ -131,11 +143,17 @@ def resnet50_servable(device: str = "cpu", dtype=torch.float32,
     from ..server import Servable
 
     if input_format not in ("float_nchw", "uint8_nhwc", "uint8_nhwc_resize",
-                            "uint8_ragged", "uint8_ragged_antialias"):
+                            "uint8_ragged", "uint8_ragged_antialias",
+                            "nv12_resize", "i420_resize"):
         raise ValueError(
             f"input_format must be 'float_nchw', 'uint8_nhwc', "
-            f"'uint8_nhwc_resize', 'uint8_ragged' or "
-            f"'uint8_ragged_antialias', got {input_format!r}")
+            f"'uint8_nhwc_resize', 'uint8_ragged', "
+            f"'uint8_ragged_antialias', 'nv12_resize' or 'i420_resize', got "
+            f"{input_format!r}")
+    if yuv_matrix != "bt601" and input_format not in _YUV_MODES:
+        raise ValueError(
+            "yuv_matrix needs input_format='nv12_resize' or 'i420_resize', "
+            f"got {input_format!r}")
     if antialias and input_format == "uint8_ragged":
         raise ValueError(
             "antialias=True is not supported with input_format="
@@ -179,6 +197,12 @@ def resnet50_servable(device: str = "cpu", dtype=torch.float32,
             IMAGENET_MEAN, IMAGENET_STD, out_dtype=dtype, layout="nchw",
             device=device, resize=256, center_crop=224,
             antialias=bool(antialias))}
+    elif input_format in _YUV_MODES:
+        images_sig = (4, [-1, -1, -1])                      # DT_UINT8
+        preprocess = {"images": Yuv420ImagePreprocess(
+            IMAGENET_MEAN, IMAGENET_STD, out_dtype=dtype, layout="nchw",
+            device=device, resize=256, center_crop=224,
+            chroma=_YUV_MODES[input_format], matrix=yuv_matrix)}
     elif input_format in _RAGGED_MODES:
         images_sig = (4, [-1])                              # DT_UINT8
         preprocess = {("images", "image_shapes"): _RAGGED_MODES[input_format](

@@ -370,6 +370,181 @@ def image_u8_resize_to_float(tensor, size, mean, std, crop=None,
     return y.to(out_dtype).contiguous()
 
 
+# (yoff, yc, rv, gu, gv, bu) of the pinned int32 YUV -> RGB conversion
+YUV_MATRICES = {
+    "bt601": (16, 298, 409, -100, -208, 516),
+    "bt709": (16, 298, 459, -55, -136, 541),
+    "bt601_full": (0, 256, 359, -88, -183, 454),
+}
+YUV_CHROMA_LAYOUTS = ("nv12", "i420")
+
+
+def _yuv420_frame_size(tensor, chroma, matrix, name):
+    """Validate a ``[N,H*3/2,W]`` uint8 batch of 4:2:0 frames; ``(N,H,W)``."""
+    if chroma not in YUV_CHROMA_LAYOUTS:
+        raise ValueError(
+            f"chroma must be 'nv12' or 'i420', got {chroma!r}")
+    if matrix not in YUV_MATRICES:
+        raise ValueError(
+            f"matrix must be one of {sorted(YUV_MATRICES)}, got {matrix!r}")
+    if not isinstance(tensor, torch.Tensor):
+        raise ValueError(f"{name} expects a torch tensor")
+    if tensor.dtype != torch.uint8:
+        raise ValueError(f"{name} expects uint8 bytes, got {tensor.dtype}")
+    if tensor.dim() != 3:
+        raise ValueError(
+            f"{name} expects [N,H*3/2,W], got rank {tensor.dim()}")
+    if not tensor.is_contiguous():
+        raise ValueError(f"{name} expects a contiguous tensor")
+    N, rows, W = (int(d) for d in tensor.shape)
+    if rows % 3 != 0:
+        raise ValueError(
+            f"{name}: a 4:2:0 frame has H*3/2 rows, got {rows} (not a "
+            "multiple of 3)")
+    H = rows // 3 * 2
+    if H % 2 != 0 or W % 2 != 0:
+        raise ValueError(
+            f"{name}: frame height and width must be even, got {H}x{W}")
+    for label, v in (("frame height", H), ("frame width", W)):
+        if not 2 <= v <= RESIZE_MAX_SIDE:
+            raise ValueError(
+                f"{name}: {label} must be in 2..{RESIZE_MAX_SIDE}, got {v}")
+    return N, H, W
+
+
+def yuv420_to_rgb_u8(tensor, chroma="nv12", matrix="bt601"):
+    """YUV 4:2:0 frames -> RGB uint8 ``[N,H,W,3]``, the pinned integer
+    conversion.
+
+    ``tensor`` is a contiguous uint8 ``[N,H*3/2,W]`` batch, ``H`` and ``W``
+    even. A frame is its ``H*W`` luma bytes followed by the quarter-size
+    chroma: ``chroma="nv12"``: ``H/2`` rows of ``W/2`` interleaved ``(U,V)``
+    pairs; ``chroma="i420"``: the flat U plane of ``(H/2)*(W/2)`` bytes, then
+    the V plane. Chroma is replicated: pixel ``(y,x)`` uses sample
+    ``(y>>1, x>>1)``. In int32, with ``D = U-128``, ``E = V-128`` and
+    ``out = clamp((sum + 128) >> 8, 0, 255)``:
+
+    ==============  ====  =========  ==============  =========
+    ``matrix``      C     R          G               B
+    ==============  ====  =========  ==============  =========
+    ``bt601``       Y-16  298C+409E  298C-100D-208E  298C+516D
+    ``bt709``       Y-16  298C+459E  298C-55D-136E   298C+541D
+    ``bt601_full``  Y     256C+359E  256C-88D-183E   256C+454D
+    ==============  ====  =========  ==============  =========
+
+    (the first two are video range, the last is full-range JFIF). A negative
+    sum clamps to 0 whichever way the shift rounds. Each channel is within 1
+    of the rounded floating-point matrix.
+
+    Plain torch integer ops, on CPU and device tensors: this is the
+    reference of :func:`image_yuv420_resize_to_float`, its CPU path, and the
+    two-step baseline it is measured against. Invalid arguments raise
+    ``ValueError``."""
+    N, H, W = _yuv420_frame_size(tensor, chroma, matrix, "yuv420_to_rgb_u8")
+    yoff, yc, rv, gu, gv, bu = YUV_MATRICES[matrix]
+    hw, q = H * W, (H // 2) * (W // 2)
+    flat = tensor.reshape(N, hw + 2 * q)
+    Y = flat[:, :hw].reshape(N, H, W).to(torch.int32)
+    if chroma == "nv12":
+        uv = flat[:, hw:].reshape(N, H // 2, W // 2, 2)
+        U, V = uv[..., 0], uv[..., 1]
+    else:
+        U = flat[:, hw:hw + q].reshape(N, H // 2, W // 2)
+        V = flat[:, hw + q:].reshape(N, H // 2, W // 2)
+
+    def up(plane):
+        return (plane.to(torch.int32) - 128).repeat_interleave(
+            2, dim=1).repeat_interleave(2, dim=2)
+
+    D, E = up(U), up(V)
+    base = yc * (Y - yoff) + 128
+    rgb = torch.stack((base + rv * E, base + gu * D + gv * E, base + bu * D),
+                      dim=-1)
+    return (rgb >> 8).clamp_(0, 255).to(torch.uint8)
+
+
+def image_yuv420_resize_to_float(tensor, size, mean, std, crop=None,
+                                 out_dtype=None, layout="nchw",
+                                 pixel_scale=1.0 / 255.0, _variant=0, *,
+                                 chroma="nv12", matrix="bt601"):
+    """Fused ingest of YUV 4:2:0 frames: conversion to RGB, bilinear resize,
+    crop and normalize in one pass. ``tensor`` is a contiguous uint8
+    ``[N,H*3/2,W]`` batch of NV12 or I420 frames (layout and ``matrix``: see
+    :func:`yuv420_to_rgb_u8`), 1.5 bytes per pixel instead of RGB's 3.
+
+    The contract, bit for bit::
+
+        image_yuv420_resize_to_float(x, size, mean, std, crop, out_dtype,
+                                     layout, pixel_scale,
+                                     chroma=chroma, matrix=matrix)
+          == image_u8_resize_to_float(yuv420_to_rgb_u8(x, chroma, matrix),
+                                      size, mean, std, crop, out_dtype,
+                                      layout, pixel_scale)
+
+    so every bilinear tap is the converted and clamped uint8 value of its
+    source pixel, and the identity-size and crop properties of
+    :func:`image_u8_resize_to_float` carry over. ``size=None`` means
+    ``(H,W)``; ``mean`` and ``std`` have 3 entries.
+
+    Device tensors run the gfx950 kernel: one launch, the RGB image never
+    exists in device memory, no eager fallback. CPU tensors run exactly the
+    two-step expression above, so CPU-only servers work too. ``H`` and ``W``
+    must be even and in 2..16384, the resized sides in 1..16384. Invalid
+    arguments raise ``ValueError`` on both paths; ``N == 0`` returns an empty
+    tensor."""
+    import numpy as np
+
+    name = "image_yuv420_resize_to_float"
+    if out_dtype is None:
+        out_dtype = torch.float32
+    if layout not in ("nchw", "nhwc"):
+        raise ValueError(f"layout must be 'nchw' or 'nhwc', got {layout!r}")
+    if out_dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError(
+            f"out_dtype must be float32, bfloat16 or float16, got {out_dtype}")
+    N, Hin, Win = _yuv420_frame_size(tensor, chroma, matrix, name)
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError(
+            f"mean/std need 3 entries (R, G, B), got {len(mean)}/{len(std)}")
+    if size is None:
+        size = (Hin, Win)
+    try:
+        Hr, Wr = (int(d) for d in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"size must be (H, W), got {size!r}") from None
+    for label, v in (("resized height", Hr), ("resized width", Wr)):
+        if not 1 <= v <= RESIZE_MAX_SIDE:
+            raise ValueError(
+                f"{name}: {label} must be in 1..{RESIZE_MAX_SIDE}, got {v}")
+    if crop is None:
+        top, left, Hc, Wc = 0, 0, Hr, Wr
+    else:
+        try:
+            top, left, Hc, Wc = (int(d) for d in crop)
+        except (TypeError, ValueError):
+            raise ValueError(
+                f"crop must be (top, left, height, width), got {crop!r}"
+            ) from None
+        if Hc < 1 or Wc < 1:
+            raise ValueError(f"crop extent must be positive, got {Hc}x{Wc}")
+        if top < 0 or left < 0 or top + Hc > Hr or left + Wc > Wr:
+            raise ValueError(
+                f"crop window (top={top}, left={left}, {Hc}x{Wc}) is not "
+                f"inside the resized image {Hr}x{Wr}")
+    scale, bias = normalization_constants(mean, std, pixel_scale)
+    if tensor.is_cuda:
+        rh = float(np.float32(Hin / Hr))
+        rw = float(np.float32(Win / Wr))
+        return require_native().yuv420_resize_normalize(
+            tensor, chroma == "i420", list(YUV_MATRICES[matrix]), rh, rw,
+            top, left, Hc, Wc, scale, bias, out_dtype, layout == "nchw",
+            int(_variant))
+    return image_u8_resize_to_float(
+        yuv420_to_rgb_u8(tensor, chroma, matrix), (Hr, Wr), mean, std,
+        crop=(top, left, Hc, Wc), out_dtype=out_dtype, layout=layout,
+        pixel_scale=pixel_scale)
+
+
 def _ragged_pairs(value, n, what, name):
     """``value`` as an int64 numpy ``[n,2]``: one pair for every image, or
     one pair per image."""

@@ -17,6 +17,8 @@
 //    triangle filter, horizontal then vertical pass over an fp32 workspace),
 //  * both resizes for ragged batches (N images of N sizes in one flat
 //    buffer, a per-image table in device memory),
+//  * the bilinear resize for YUV 4:2:0 frames (NV12 / I420, 1.5 bytes per
+//    pixel), converted to RGB with integer arithmetic while LDS is filled,
 //  * fused masked mean-pool (+ L2 normalize) head: [B,S,H] hidden state ->
 //    fp32 [B,H] sentence embeddings, so responses ship S x fewer bytes,
 // plus the host-side staging machinery: pinned double-buffered
@@ -865,6 +867,262 @@ u8_ragged_resize_normalize_kernel(
     } else if (active) {
       resize_run<CVT, C, NCHW>(img + y0 * row_bytes, img + y1 * row_bytes, 0,
                                wy, ox0, dst, plane, q);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// YUV 4:2:0 source side (NV12 / I420) of the bilinear resize + crop ingest
+// ---------------------------------------------------------------------------
+// One frame is Hin*3/2 rows of Win bytes, Hin and Win even: the Y plane
+// (Hin*Win bytes), then NV12: Hin/2 rows of Win/2 interleaved (U,V) pairs, or
+// I420: the U plane of (Hin/2)*(Win/2) flat bytes, then the V plane. Frames
+// lie back to back. Luma pixel (y,x) uses chroma sample (y>>1, x>>1), and is
+// converted in int32 (coefficients in Yuv420Coef, three matrices on the host):
+//
+//   C = Y - yoff   D = U - 128   E = V - 128
+//   R = clamp((yc*C        + rv*E + 128) >> 8, 0, 255)
+//   G = clamp((yc*C + gu*D + gv*E + 128) >> 8, 0, 255)
+//   B = clamp((yc*C + bu*D        + 128) >> 8, 0, 255)
+//
+// A negative sum clamps to 0 however the shift rounds. Every bilinear tap is
+// that clamped uint8 value; everything after it is resize_run, unchanged, so
+// the result is bit-identical to u8_nhwc_resize_normalize_kernel<CVT,3,NCHW>
+// on the converted RGB tensor, which never exists in memory.
+//
+// Tile geometry, work items, the grid-stride loop and the store path are those
+// of the RGB kernel. The tap paths:
+//  * LDS path: the workgroup converts while it fills. An LDS span holds the
+//    RGB bytes (3 per pixel) of one source row from column xe = xs_lo & ~1, so
+//    a 16-pixel fill chunk starts at an even column and never splits a chroma
+//    pair. A chunk is one 16 B luma load and 16 B (NV12) or 2 x 8 B (I420) of
+//    chroma, converted in registers and written as three 16 B LDS stores.
+//    Luma and chroma of a chunk have unrelated alignments (odd row strides,
+//    odd plane bases, any storage offset), so the global loads are unaligned
+//    vector loads (memcpy); a chunk whose loads would pass the end of the
+//    tensor is read bytewise, in bounds. Loads may run past the span or the
+//    row end into bytes of the same tensor that no tap reads.
+//  * direct path: Yuv420Row converts per tap from global memory. Taken when
+//    the host found that the tile's spans exceed kResizeLdsBytes (span_px ==
+//    0), or when a tile's span does not fit the estimate.
+struct Yuv420Coef {
+  int yoff, yc, rv, gu, gv, bu;
+};
+
+struct Yuv420ResizeParams {
+  U8ResizeParams r;   // span_stride: LDS bytes per span, 48 per fill chunk
+  Yuv420Coef k;
+  int span_px;        // pixels per LDS span (multiple of 16), 0: direct
+};
+
+constexpr int kYuvChunkPx = 16;
+
+// clamp(v >> 8, 0, 255), written clamp first: the same value for every v.
+// The shift-then-clamp form is selected as v_ashr_pk_u8_i32 for pairs of
+// values by hipcc (ROCm 7.2), and the packed bytes came out wrong on MI355X.
+__device__ __forceinline__ uint32_t yuv_clamp8(int v) {
+  return uint32_t(min(max(v, 0), 0xffff)) >> 8;
+}
+
+// One source row in global memory. `u`/`v` point at the row's first chroma
+// sample, `cstep` bytes apart (NV12: 2 with v = u + 1; I420: 1).
+struct Yuv420Row {
+  const uint8_t* y;
+  const uint8_t* u;
+  const uint8_t* v;
+  int cstep;
+  // the converted pixel x as floats, ready to blend
+  __device__ __forceinline__ void rgb(int x, const Yuv420Coef& k,
+                                      float (&o)[3]) const {
+    const int co = (x >> 1) * cstep;
+    const int base = k.yc * (int(y[x]) - k.yoff) + 128;
+    const int D = int(u[co]) - 128, E = int(v[co]) - 128;
+    o[0] = float(yuv_clamp8(base + k.rv * E));
+    o[1] = float(yuv_clamp8(base + k.gu * D + k.gv * E));
+    o[2] = float(yuv_clamp8(base + k.bu * D));
+  }
+};
+
+// resize_run for the direct path: the same fp32 operations in the same order,
+// on taps that are fetched through Yuv420Row and converted once per pixel.
+template <typename CVT, bool NCHW>
+__device__ __forceinline__ void yuv420_resize_run_direct(
+    const Yuv420Row& r0, const Yuv420Row& r1, const Yuv420Coef& kf, float wy,
+    int ox0, typename CVT::Out* __restrict__ dst, int64_t plane,
+    const U8ResizeParams& p) {
+  using Out = typename CVT::Out;
+  constexpr int C = 3;
+  Out vout[C * kResizePx];   // NCHW: [c][k], NHWC: [k][c]
+#pragma unroll
+  for (int k = 0; k < kResizePx; ++k) {
+    const int ox = min(ox0 + k, p.Wc - 1);
+    int x0, x1;
+    float wx;
+    resize_tap(ox, p.left, p.rw, p.Win, x0, x1, wx);
+    float p00[C], p01[C], p10[C], p11[C];
+    r0.rgb(x0, kf, p00);
+    r0.rgb(x1, kf, p01);
+    r1.rgb(x0, kf, p10);
+    r1.rgb(x1, kf, p11);
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const float t =
+          __fadd_rn(p00[c], __fmul_rn(wx, __fsub_rn(p01[c], p00[c])));
+      const float b =
+          __fadd_rn(p10[c], __fmul_rn(wx, __fsub_rn(p11[c], p10[c])));
+      const float v = __fadd_rn(t, __fmul_rn(wy, __fsub_rn(b, t)));
+      vout[NCHW ? c * kResizePx + k : k * C + c] =
+          CVT::cvt(__fadd_rn(__fmul_rn(v, p.scale[c]), p.bias[c]));
+    }
+  }
+  resize_store_run<Out, C, NCHW>(vout, ox0, p.Wc, dst, plane);
+}
+
+// 16 luma bytes `yw` and their 8 chroma samples `cw` (NV12: U,V interleaved;
+// I420: 8 U bytes then 8 V bytes) -> 48 RGB bytes `o`.
+template <bool I420>
+__device__ __forceinline__ void yuv420_convert_chunk(
+    const uint32_t (&yw)[4], const uint32_t (&cw)[4], const Yuv420Coef& k,
+    uint32_t (&o)[12]) {
+#pragma unroll
+  for (int w = 0; w < 12; ++w) o[w] = 0;
+#pragma unroll
+  for (int pr = 0; pr < kYuvChunkPx / 2; ++pr) {
+    const int ub = I420 ? pr : 2 * pr, vb = I420 ? 8 + pr : 2 * pr + 1;
+    const int D = int((cw[ub >> 2] >> (8 * (ub & 3))) & 0xffu) - 128;
+    const int E = int((cw[vb >> 2] >> (8 * (vb & 3))) & 0xffu) - 128;
+    const int rE = k.rv * E, gDE = k.gu * D + k.gv * E, bD = k.bu * D;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int j = 2 * pr + h;
+      const int Y = int((yw[j >> 2] >> (8 * (j & 3))) & 0xffu);
+      const int base = k.yc * (Y - k.yoff) + 128;
+      const uint32_t rgb[3] = {yuv_clamp8(base + rE), yuv_clamp8(base + gDE),
+                               yuv_clamp8(base + bD)};
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int b = 3 * j + c;
+        o[b >> 2] |= rgb[c] << (8 * (b & 3));
+      }
+    }
+  }
+}
+
+template <typename CVT, bool NCHW, bool I420>
+__global__ void __launch_bounds__(kResizeBlock)
+yuv420_resize_normalize_kernel(
+    const uint8_t* __restrict__ in, typename CVT::Out* __restrict__ out,
+    int64_t N, Yuv420ResizeParams pp) {
+  using Out = typename CVT::Out;
+  constexpr int C = 3;
+  __shared__ __attribute__((aligned(16))) uint8_t lds[kResizeLdsBytes];
+  static_assert(kResizePx % (16 / int(sizeof(Out))) == 0,
+                "a lane run must fill whole 16 B stores");
+  const U8ResizeParams& p = pp.r;
+  const int twl = 1 << p.twl_log2;               // lane runs per tile row
+  const int tr = kResizeBlock >> p.twl_log2;     // rows per tile
+  const int tw = twl * kResizePx;                // columns per tile
+  const int r = int(threadIdx.x) >> p.twl_log2;
+  const int j = int(threadIdx.x) & (twl - 1);
+  const int64_t plane = int64_t(p.Hc) * p.Wc;
+  const int64_t y_bytes = int64_t(p.Hin) * p.Win;
+  const int64_t c_bytes = int64_t(p.Hin >> 1) * (p.Win >> 1);   // one plane
+  const int64_t frame_bytes = y_bytes + 2 * c_bytes;
+  const int64_t c_row = I420 ? p.Win >> 1 : p.Win;   // chroma row stride
+  const int cstep = I420 ? 1 : 2;
+  const uint8_t* const in_end = in + N * frame_bytes;
+  const int64_t items = N * p.tiles_y * p.tiles_x;
+  for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+    const int tx = int(item % p.tiles_x);
+    const int ty = int((item / p.tiles_x) % p.tiles_y);
+    const int64_t n = item / (int64_t(p.tiles_x) * p.tiles_y);
+    const uint8_t* img = in + n * frame_bytes;
+    const uint8_t* uimg = img + y_bytes;
+    const uint8_t* vimg = I420 ? uimg + c_bytes : uimg + 1;
+    const int oy = ty * tr + r;
+    const int ox0 = tx * tw + j * kResizePx;
+    const bool active = oy < p.Hc && ox0 < p.Wc;
+
+    // source column span of the tile, the same for every row of it
+    int xs_lo, xs_hi, unused;
+    float unused_w;
+    resize_tap(tx * tw, p.left, p.rw, p.Win, xs_lo, unused, unused_w);
+    resize_tap(min(tx * tw + tw, p.Wc) - 1, p.left, p.rw, p.Win, unused,
+               xs_hi, unused_w);
+    const int xe = xs_lo & ~1;   // spans start on a chroma pair
+    // uniform in the workgroup: the barriers below are not divergent
+    const bool use_lds = pp.span_px > 0 && xs_hi + 1 - xe <= pp.span_px;
+
+    int y0 = 0, y1 = 0;
+    float wy = 0.f;
+    if (active) resize_tap(oy, p.top, p.rh, p.Hin, y0, y1, wy);
+    Out* dst = NCHW
+        ? out + (n * C * p.Hc + oy) * p.Wc + ox0
+        : out + ((n * p.Hc + oy) * p.Wc + ox0) * C;
+
+    if (use_lds) {
+      const int nchunks = pp.span_px / kYuvChunkPx;
+      const int rows_here = min(tr, p.Hc - ty * tr);
+      const int total = 2 * rows_here * nchunks;
+      for (int idx = int(threadIdx.x); idx < total; idx += kResizeBlock) {
+        const int s = idx / nchunks;           // span: tile row s>>1, y(s&1)
+        const int xc = xe + (idx - s * nchunks) * kYuvChunkPx;
+        if (xc > xs_hi) continue;
+        int sy0, sy1;
+        float sw;
+        resize_tap(ty * tr + (s >> 1), p.top, p.rh, p.Hin, sy0, sy1, sw);
+        const int sy = (s & 1) ? sy1 : sy0;
+        const uint8_t* ya = img + int64_t(sy) * p.Win + xc;
+        const int64_t co = int64_t(sy >> 1) * c_row + (xc >> 1) * cstep;
+        const uint8_t* ua = uimg + co;
+        const uint8_t* va = vimg + co;
+        uint32_t yw[4], cw[4];
+        // the V (NV12: U,V) bytes end last: if they are inside, all are
+        if ((I420 ? va + 8 : ua + 16) <= in_end && ya + 16 <= in_end) {
+          __builtin_memcpy(yw, ya, 16);
+          if constexpr (I420) {
+            __builtin_memcpy(cw, ua, 8);
+            __builtin_memcpy(cw + 2, va, 8);
+          } else {
+            __builtin_memcpy(cw, ua, 16);
+          }
+        } else {
+          // the last chunks of the tensor: stay inside it
+#pragma unroll
+          for (int w = 0; w < 4; ++w) yw[w] = cw[w] = 0;
+          for (int b = 0; b < 16; ++b) {
+            const uint8_t* ca = I420 ? (b < 8 ? ua + b : va + (b - 8))
+                                     : ua + b;
+            const uint32_t yb = ya + b < in_end ? ya[b] : 0u;
+            const uint32_t cb = ca < in_end ? *ca : 0u;
+            yw[b >> 2] |= yb << (8 * (b & 3));
+            cw[b >> 2] |= cb << (8 * (b & 3));
+          }
+        }
+        uint32_t o[12];
+        yuv420_convert_chunk<I420>(yw, cw, pp.k, o);
+        int4* l = reinterpret_cast<int4*>(
+            lds + s * p.span_stride + (xc - xe) * C);
+#pragma unroll
+        for (int v = 0; v < 3; ++v)
+          l[v] = *reinterpret_cast<const int4*>(o + 4 * v);
+      }
+      __syncthreads();
+      if (active) {
+        const uint8_t* l0 = lds + (2 * r) * p.span_stride;
+        const uint8_t* l1 = lds + (2 * r + 1) * p.span_stride;
+        resize_run<CVT, C, NCHW>(l0, l1, xe, wy, ox0, dst, plane, p);
+      }
+      __syncthreads();   // lds is refilled by the next work item
+    } else if (active) {
+      const Yuv420Row r0{img + int64_t(y0) * p.Win,
+                         uimg + int64_t(y0 >> 1) * c_row,
+                         vimg + int64_t(y0 >> 1) * c_row, cstep};
+      const Yuv420Row r1{img + int64_t(y1) * p.Win,
+                         uimg + int64_t(y1 >> 1) * c_row,
+                         vimg + int64_t(y1 >> 1) * c_row, cstep};
+      yuv420_resize_run_direct<CVT, NCHW>(r0, r1, pp.k, wy, ox0, dst, plane,
+                                          p);
     }
   }
 }
@@ -1955,6 +2213,112 @@ at::Tensor u8_nhwc_resize_normalize(
   if (out_dtype == at::kFloat) by_channels(IdF32{});
   else if (out_dtype == at::kBFloat16) by_channels(F32ToBf16{});
   else by_channels(F32ToF16{});
+  HIP_CHECK(hipGetLastError());
+  return out;
+}
+
+// YUV 4:2:0 source side of the fused bilinear resize + crop ingest; see the
+// kernel section. `in` is uint8 [N, Hin*3/2, Win] with Hin and Win even
+// (validated by ops.image_yuv420_resize_to_float, like the crop window),
+// `i420` picks planar chroma over NV12's interleaved pairs and `coef` is
+// (yoff, yc, rv, gu, gv, bu) of the int32 conversion. The other arguments are
+// those of u8_nhwc_resize_normalize with C = 3.
+at::Tensor yuv420_resize_normalize(
+    const at::Tensor& in, bool i420, std::vector<int64_t> coef, double rh,
+    double rw, int64_t top, int64_t left, int64_t Hc, int64_t Wc,
+    std::vector<double> scale, std::vector<double> bias,
+    at::ScalarType out_dtype, bool out_nchw, int64_t variant) {
+  TORCH_CHECK(in.is_cuda() && in.dim() == 3 && in.is_contiguous() &&
+              in.scalar_type() == at::kByte,
+              "yuv420_resize_normalize expects a contiguous uint8 device "
+              "tensor [N,H*3/2,W]");
+  constexpr int64_t kMaxSide = 16384;
+  constexpr int64_t C = 3;
+  const int64_t N = in.size(0), Win = in.size(2);
+  TORCH_CHECK(in.size(1) % 3 == 0,
+              "yuv420_resize_normalize: rows must be a multiple of 3");
+  const int64_t Hin = in.size(1) / 3 * 2;
+  TORCH_CHECK(Hin >= 2 && Hin <= kMaxSide && Win >= 2 && Win <= kMaxSide &&
+              Hin % 2 == 0 && Win % 2 == 0,
+              "yuv420_resize_normalize: frame sides must be even and in "
+              "2..16384");
+  TORCH_CHECK(Hc >= 1 && Wc >= 1 && top >= 0 && left >= 0 &&
+              top + Hc <= kMaxSide && left + Wc <= kMaxSide,
+              "yuv420_resize_normalize: bad crop window");
+  TORCH_CHECK(rh > 0.0 && rw > 0.0,
+              "yuv420_resize_normalize: ratios must be positive");
+  TORCH_CHECK(int64_t(scale.size()) == C && int64_t(bias.size()) == C,
+              "yuv420_resize_normalize: scale/bias need 3 values");
+  TORCH_CHECK(coef.size() == 6,
+              "yuv420_resize_normalize: coef needs 6 values");
+  for (int64_t v : coef)   // sums stay far inside int32
+    TORCH_CHECK(v >= -4096 && v <= 4096,
+                "yuv420_resize_normalize: coefficient out of range");
+  TORCH_CHECK(out_dtype == at::kFloat || out_dtype == at::kBFloat16 ||
+              out_dtype == at::kHalf,
+              "yuv420_resize_normalize: out_dtype must be f32, bf16 or f16");
+  auto out = out_nchw
+      ? at::empty({N, C, Hc, Wc}, in.options().dtype(out_dtype))
+      : at::empty({N, Hc, Wc, C}, in.options().dtype(out_dtype));
+  if (N == 0) return out;  // zero grid: never launch
+
+  Yuv420ResizeParams pp{};
+  U8ResizeParams& p = pp.r;
+  for (int64_t c = 0; c < C; ++c) {
+    p.scale[c] = float(scale[c]);
+    p.bias[c] = float(bias[c]);
+  }
+  pp.k = Yuv420Coef{int(coef[0]), int(coef[1]), int(coef[2]), int(coef[3]),
+                    int(coef[4]), int(coef[5])};
+  p.rh = float(rh);
+  p.rw = float(rw);
+  p.Hin = int(Hin); p.Win = int(Win);
+  p.Hc = int(Hc); p.Wc = int(Wc);
+  p.top = int(top); p.left = int(left);
+  // tile geometry from Wc, as in u8_nhwc_resize_normalize
+  const int64_t runs = (Wc + kResizePx - 1) / kResizePx;
+  p.twl_log2 = kResizeMinTwlLog2;
+  while (p.twl_log2 < kResizeMaxTwlLog2 && (int64_t(1) << p.twl_log2) < runs)
+    ++p.twl_log2;
+  const int64_t tw = (int64_t(1) << p.twl_log2) * kResizePx;
+  const int64_t tr = kResizeBlock >> p.twl_log2;
+  p.tiles_x = int((Wc + tw - 1) / tw);
+  p.tiles_y = int((Hc + tr - 1) / tr);
+  // pixels per LDS span: the widest span of a tile (an upper estimate; the
+  // kernel checks each tile's own span against it) plus one for the even
+  // start column, in whole fill chunks of 3 LDS bytes per pixel
+  const int64_t span_px = std::min<int64_t>(
+      Win, int64_t(std::ceil(double(std::min(tw, Wc)) * double(p.rw))) + 3);
+  const int64_t chunks = (span_px + 1 + kYuvChunkPx - 1) / kYuvChunkPx;
+  const int64_t span_stride = chunks * kYuvChunkPx * C;
+  const bool direct =
+      variant == 1 || 2 * tr * span_stride > kResizeLdsBytes;
+  p.span_stride = direct ? 0 : int(span_stride);
+  pp.span_px = direct ? 0 : int(chunks * kYuvChunkPx);
+
+  const int64_t items = N * p.tiles_y * p.tiles_x;
+  const int grid = int(std::min<int64_t>(items, 2048));
+  const auto* src = static_cast<const uint8_t*>(in.const_data_ptr());
+
+  auto launch = [&](auto cvt_tag, auto nchw_tag, auto i420_tag) {
+    using CVT = decltype(cvt_tag);
+    hipLaunchKernelGGL(
+        (yuv420_resize_normalize_kernel<CVT, decltype(nchw_tag)::value,
+                                        decltype(i420_tag)::value>),
+        dim3(grid), dim3(kResizeBlock), 0, current_stream(), src,
+        reinterpret_cast<typename CVT::Out*>(out.mutable_data_ptr()), N, pp);
+  };
+  auto by_chroma = [&](auto cvt_tag, auto nchw_tag) {
+    if (i420) launch(cvt_tag, nchw_tag, std::true_type{});
+    else launch(cvt_tag, nchw_tag, std::false_type{});
+  };
+  auto by_layout = [&](auto cvt_tag) {
+    if (out_nchw) by_chroma(cvt_tag, std::true_type{});
+    else by_chroma(cvt_tag, std::false_type{});
+  };
+  if (out_dtype == at::kFloat) by_layout(IdF32{});
+  else if (out_dtype == at::kBFloat16) by_layout(F32ToBf16{});
+  else by_layout(F32ToF16{});
   HIP_CHECK(hipGetLastError());
   return out;
 }

@@ -9,6 +9,9 @@ runs the fused dequantize + normalize + NCHW kernel
 fused bilinear resize + crop + normalize + NCHW kernel
 (``ops.image_u8_resize_to_float``) on images of any size; ``antialias=True``
 selects the antialiased resize kernels for downscaled photos.
+``Yuv420ImagePreprocess`` takes what decoders emit, NV12 or I420 frames at
+1.5 bytes per pixel, and converts them to RGB inside the same bilinear
+resize kernel (``ops.image_yuv420_resize_to_float``).
 ``RaggedImagePreprocess`` is the mixed-size case: one request carries N
 images of N different sizes packed back to back (``pack_ragged_images``) and
 one kernel launch (``ops.image_u8_ragged_resize_to_float``) turns them into
@@ -154,6 +157,74 @@ class ImagePreprocess:
             x, size, self.mean, self.std, crop=self.crop_window(*size),
             out_dtype=self.out_dtype, layout=self.layout,
             pixel_scale=self.pixel_scale, antialias=self.antialias)
+
+
+class Yuv420ImagePreprocess:
+    """uint8 ``[N,H*3/2,W]`` YUV 4:2:0 frames -> normalized float tensor.
+
+    Clients ship what a video or JPEG decoder emits, NV12
+    (``chroma="nv12"``) or I420 (``chroma="i420"``) frames, 1.5 bytes per
+    pixel instead of RGB's 3, and the server converts, resizes, crops and
+    normalizes in one kernel (``ops.image_yuv420_resize_to_float``; frame
+    layout and ``matrix``: ``ops.yuv420_to_rgb_u8``). The result is exactly
+    what :class:`ImagePreprocess` with the same arguments gives for the
+    converted RGB frames.
+
+    Accepts a numpy array or a torch tensor, on CPU or device. With
+    ``device`` set, the **uint8** bytes are moved there first. ``resize`` and
+    ``center_crop`` follow the rules of :class:`ImagePreprocess`, applied to
+    the frame's ``(H, W)``. Wrong dtype, rank or frame geometry raise
+    ``ValueError`` (servers answer INVALID_ARGUMENT)."""
+
+    def __init__(self, mean, std, out_dtype=None, layout: str = "nchw",
+                 pixel_scale: float = 1.0 / 255.0, device=None,
+                 resize=None, center_crop=None, chroma: str = "nv12",
+                 matrix: str = "bt601"):
+        self._rule = ImagePreprocess(
+            mean, std, out_dtype=out_dtype, layout=layout,
+            pixel_scale=pixel_scale, device=device, resize=resize,
+            center_crop=center_crop)
+        rule = self._rule
+        self.mean, self.std = rule.mean, rule.std
+        self.out_dtype, self.layout = rule.out_dtype, rule.layout
+        self.pixel_scale, self.device = rule.pixel_scale, rule.device
+        self.resize, self.center_crop = rule.resize, rule.center_crop
+        if len(self.mean) != 3 or len(self.std) != 3:
+            raise ValueError(
+                "mean/std need 3 entries (R, G, B), got "
+                f"{len(self.mean)}/{len(self.std)}")
+        if chroma not in ops.YUV_CHROMA_LAYOUTS:
+            raise ValueError(
+                f"chroma must be 'nv12' or 'i420', got {chroma!r}")
+        if matrix not in ops.YUV_MATRICES:
+            raise ValueError(
+                f"matrix must be one of {sorted(ops.YUV_MATRICES)}, got "
+                f"{matrix!r}")
+        self.chroma, self.matrix = chroma, matrix
+
+    def resized_size(self, height: int, width: int):
+        """``(Hr, Wr)`` of the resized image for a frame of this size."""
+        return self._rule.resized_size(height, width)
+
+    def crop_window(self, resized_height: int, resized_width: int):
+        """``(top, left, Hc, Wc)`` inside the resized image, or ``None``."""
+        return self._rule.crop_window(resized_height, resized_width)
+
+    def __call__(self, x):
+        x = _as_tensor(x)
+        if self.device is not None and x.dtype == torch.uint8:
+            x = x.to(self.device)
+        if x.dim() != 3 or x.shape[1] < 3 or x.shape[1] % 3 != 0 or \
+                x.shape[2] < 2:
+            raise ValueError(
+                "YUV 4:2:0 input must be [N,H*3/2,W] with non-empty frames, "
+                f"got shape {list(x.shape)}")
+        size = self.resized_size(int(x.shape[1]) // 3 * 2, int(x.shape[2]))
+        return ops.image_yuv420_resize_to_float(
+            x, size, self.mean, self.std, crop=self.crop_window(*size),
+            out_dtype=self.out_dtype, layout=self.layout,
+            pixel_scale=self.pixel_scale, chroma=self.chroma,
+            matrix=self.matrix)
 
 
 class RaggedImagePreprocess:

@@ -20,8 +20,11 @@ On-disk version-directory formats understood by the default loader:
                                "uint8_nhwc_resize", "uint8_ragged": N
                                images of N sizes in one request, or
                                "uint8_ragged_antialias": the same with the
-                               antialiased filter) and "antialias"
+                               antialiased filter, "nv12_resize" or
+                               "i420_resize": YUV 4:2:0 frames), "antialias"
                                (resnet50, with "uint8_nhwc_resize"),
+                               "yuv_matrix" (resnet50, with the YUV modes:
+                               "bt601", "bt709" or "bt601_full"),
                                "output_format" (resnet50: "logits" or
                                "topk"; bert_base: "hidden" or
                                "sentence_embedding"), "top_k" (resnet50,
@@ -177,7 +180,7 @@ def default_loader(name: str, version_dir: str,
             from .models import resnet50_servable
             modes = {k: cfg[k]
                      for k in ("input_format", "antialias", "output_format",
-                               "top_k")
+                               "top_k", "yuv_matrix")
                      if k in cfg}
             servable = resnet50_servable(device, **modes)
         elif family == "bert_base":
