@@ -14,7 +14,10 @@ from ..preprocess import (IMAGENET_MEAN, IMAGENET_STD,
 
 _RAGGED_MODES = {"uint8_ragged": RaggedImagePreprocess,
                  "uint8_ragged_antialias": AntialiasedRaggedImagePreprocess}
-_YUV_MODES = {"nv12_resize": "nv12", "i420_resize": "i420"}
+# mode -> (chroma layout, antialiased filter)
+_YUV_MODES = {"nv12_resize": ("nv12", False), "i420_resize": ("i420", False),
+              "nv12_resize_antialias": ("nv12", True),
+              "i420_resize_antialias": ("i420", True)}
 
 
 class Bottleneck(nn.Module):
@@ -128,7 +131,15 @@ def resnet50_servable(device: str = "cpu", dtype=torch.float32,
     (``Yuv420ImagePreprocess(resize=256, center_crop=224)``): exactly what
     ``uint8_nhwc_resize`` gives for the converted RGB frames
     (``ops.yuv420_to_rgb_u8``). The filter is bilinear; ``antialias=True`` is
-    rejected, and so is a non-default ``yuv_matrix`` in every other mode.
+    rejected, because the antialiased counterparts have names of their own:
+    ``input_format="nv12_resize_antialias"`` / ``"i420_resize_antialias"``:
+    the same input, resized with the antialiased filter in two kernel
+    launches, the first of which converts
+    (``Yuv420ImagePreprocess(resize=256, center_crop=224, antialias=True)``):
+    exactly what ``uint8_nhwc_resize`` with ``antialias=True`` gives for the
+    converted RGB frames. ``yuv_matrix`` is accepted; the mode name carries
+    the filter, so ``antialias=True`` on top of it is rejected. A non-default
+    ``yuv_matrix`` is rejected in every mode but these four.
 
     ``output_format="logits"`` (default): the only output is "logits",
     DT_FLOAT (N,1000).
@@ -144,21 +155,28 @@ def resnet50_servable(device: str = "cpu", dtype=torch.float32,
 
     if input_format not in ("float_nchw", "uint8_nhwc", "uint8_nhwc_resize",
                             "uint8_ragged", "uint8_ragged_antialias",
-                            "nv12_resize", "i420_resize"):
+                            *_YUV_MODES):
         raise ValueError(
             f"input_format must be 'float_nchw', 'uint8_nhwc', "
             f"'uint8_nhwc_resize', 'uint8_ragged', "
-            f"'uint8_ragged_antialias', 'nv12_resize' or 'i420_resize', got "
+            f"'uint8_ragged_antialias', 'nv12_resize', 'i420_resize', "
+            f"'nv12_resize_antialias' or 'i420_resize_antialias', got "
             f"{input_format!r}")
     if yuv_matrix != "bt601" and input_format not in _YUV_MODES:
         raise ValueError(
-            "yuv_matrix needs input_format='nv12_resize' or 'i420_resize', "
-            f"got {input_format!r}")
+            "yuv_matrix needs a YUV input_format ('nv12_resize', "
+            "'i420_resize' or their '_antialias' counterparts), got "
+            f"{input_format!r}")
     if antialias and input_format == "uint8_ragged":
         raise ValueError(
             "antialias=True is not supported with input_format="
             "'uint8_ragged': antialiased ragged batches are "
             "input_format='uint8_ragged_antialias'")
+    if antialias and input_format in _YUV_MODES:
+        raise ValueError(
+            "antialias=True is not supported with input_format="
+            f"{input_format!r}: antialiased YUV frames are input_format="
+            f"'{_YUV_MODES[input_format][0]}_resize_antialias'")
     if antialias and input_format != "uint8_nhwc_resize":
         raise ValueError(
             "antialias=True needs input_format='uint8_nhwc_resize', got "
@@ -202,7 +220,8 @@ def resnet50_servable(device: str = "cpu", dtype=torch.float32,
         preprocess = {"images": Yuv420ImagePreprocess(
             IMAGENET_MEAN, IMAGENET_STD, out_dtype=dtype, layout="nchw",
             device=device, resize=256, center_crop=224,
-            chroma=_YUV_MODES[input_format], matrix=yuv_matrix)}
+            chroma=_YUV_MODES[input_format][0], matrix=yuv_matrix,
+            antialias=_YUV_MODES[input_format][1])}
     elif input_format in _RAGGED_MODES:
         images_sig = (4, [-1])                              # DT_UINT8
         preprocess = {("images", "image_shapes"): _RAGGED_MODES[input_format](

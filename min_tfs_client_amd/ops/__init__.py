@@ -466,7 +466,8 @@ def yuv420_to_rgb_u8(tensor, chroma="nv12", matrix="bt601"):
 def image_yuv420_resize_to_float(tensor, size, mean, std, crop=None,
                                  out_dtype=None, layout="nchw",
                                  pixel_scale=1.0 / 255.0, _variant=0, *,
-                                 chroma="nv12", matrix="bt601"):
+                                 chroma="nv12", matrix="bt601",
+                                 antialias=False, _ws_cap_bytes=None):
     """Fused ingest of YUV 4:2:0 frames: conversion to RGB, bilinear resize,
     crop and normalize in one pass. ``tensor`` is a contiguous uint8
     ``[N,H*3/2,W]`` batch of NV12 or I420 frames (layout and ``matrix``: see
@@ -486,8 +487,21 @@ def image_yuv420_resize_to_float(tensor, size, mean, std, crop=None,
     :func:`image_u8_resize_to_float` carry over. ``size=None`` means
     ``(H,W)``; ``mean`` and ``std`` have 3 entries.
 
-    Device tensors run the gfx950 kernel: one launch, the RGB image never
-    exists in device memory, no eager fallback. CPU tensors run exactly the
+    ``antialias=True`` (keyword only) keeps that contract with
+    ``antialias=True`` on the right-hand side too, bit for bit::
+
+        image_yuv420_resize_to_float(..., chroma=c, matrix=m, antialias=True)
+          == image_u8_resize_to_float(yuv420_to_rgb_u8(x, c, m), ...,
+                                      antialias=True)
+
+    Every tap of the horizontal pass is the converted, clamped uint8 value of
+    its source pixel, widened to fp32; the tap order, the one division by
+    ``tot``, the vertical pass and the normalization are those of the RGB
+    antialiased op, whose vertical kernel it reuses.
+
+    Device tensors run the gfx950 kernels: one launch (two for
+    ``antialias=True``: a horizontal pass that converts, then the vertical
+    pass), the RGB image never exists in device memory, no eager fallback. CPU tensors run exactly the
     two-step expression above, so CPU-only servers work too. ``H`` and ``W``
     must be even and in 2..16384, the resized sides in 1..16384. Invalid
     arguments raise ``ValueError`` on both paths; ``N == 0`` returns an empty
@@ -535,6 +549,11 @@ def image_yuv420_resize_to_float(tensor, size, mean, std, crop=None,
     if tensor.is_cuda:
         rh = float(np.float32(Hin / Hr))
         rw = float(np.float32(Win / Wr))
+        if antialias:
+            return require_native().yuv420_resize_aa_normalize(
+                tensor, chroma == "i420", list(YUV_MATRICES[matrix]), rh, rw,
+                top, left, Hc, Wc, scale, bias, out_dtype, layout == "nchw",
+                int(_variant), int(_ws_cap_bytes or 0))
         return require_native().yuv420_resize_normalize(
             tensor, chroma == "i420", list(YUV_MATRICES[matrix]), rh, rw,
             top, left, Hc, Wc, scale, bias, out_dtype, layout == "nchw",
@@ -542,7 +561,7 @@ def image_yuv420_resize_to_float(tensor, size, mean, std, crop=None,
     return image_u8_resize_to_float(
         yuv420_to_rgb_u8(tensor, chroma, matrix), (Hr, Wr), mean, std,
         crop=(top, left, Hc, Wc), out_dtype=out_dtype, layout=layout,
-        pixel_scale=pixel_scale)
+        pixel_scale=pixel_scale, antialias=bool(antialias))
 
 
 def _ragged_pairs(value, n, what, name):

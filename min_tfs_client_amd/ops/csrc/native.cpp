@@ -49,6 +49,12 @@ at::Tensor u8_nhwc_resize_aa_normalize(
     int64_t Hc, int64_t Wc, std::vector<double> scale,
     std::vector<double> bias, at::ScalarType out_dtype, bool out_nchw,
     int64_t ws_cap_bytes);
+at::Tensor yuv420_resize_aa_normalize(
+    const at::Tensor& in, bool i420, std::vector<int64_t> coef, double rh,
+    double rw, int64_t top, int64_t left, int64_t Hc, int64_t Wc,
+    std::vector<double> scale, std::vector<double> bias,
+    at::ScalarType out_dtype, bool out_nchw, int64_t variant,
+    int64_t ws_cap_bytes);
 at::Tensor u8_ragged_resize_aa_normalize(
     const at::Tensor& in, const at::Tensor& table, int64_t C, int64_t Hc,
     int64_t Wc, std::vector<double> scale, std::vector<double> bias,
@@ -677,6 +683,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("left"), py::arg("crop_h"), py::arg("crop_w"),
         py::arg("scale"), py::arg("bias"), py::arg("out_dtype"),
         py::arg("out_nchw") = true, py::arg("ws_cap_bytes") = 0);
+  m.def("yuv420_resize_aa_normalize", &mi355x::yuv420_resize_aa_normalize,
+        py::arg("input"), py::arg("i420"), py::arg("coef"), py::arg("rh"),
+        py::arg("rw"), py::arg("top"), py::arg("left"), py::arg("crop_h"),
+        py::arg("crop_w"), py::arg("scale"), py::arg("bias"),
+        py::arg("out_dtype"), py::arg("out_nchw") = true,
+        py::arg("variant") = 0, py::arg("ws_cap_bytes") = 0);
   m.def("u8_ragged_resize_aa_normalize",
         &mi355x::u8_ragged_resize_aa_normalize, py::arg("input"),
         py::arg("table"), py::arg("channels"), py::arg("crop_h"),

@@ -1008,6 +1008,42 @@ __device__ __forceinline__ void yuv420_convert_chunk(
   }
 }
 
+// One fill chunk: the 16 luma bytes at `ya` and their 8 chroma samples at
+// `ua`/`va` -> 48 RGB bytes at `l` (LDS, 16 B-aligned). Unaligned vector loads
+// when they stay below `in_end`, the end of the tensor; else bytewise, in
+// bounds, zeros for what lies past it.
+template <bool I420>
+__device__ __forceinline__ void yuv420_fill_chunk(
+    const uint8_t* ya, const uint8_t* ua, const uint8_t* va,
+    const uint8_t* in_end, const Yuv420Coef& k, int4* l) {
+  uint32_t yw[4], cw[4];
+  // the V (NV12: U,V) bytes end last: if they are inside, all are
+  if ((I420 ? va + 8 : ua + 16) <= in_end && ya + 16 <= in_end) {
+    __builtin_memcpy(yw, ya, 16);
+    if constexpr (I420) {
+      __builtin_memcpy(cw, ua, 8);
+      __builtin_memcpy(cw + 2, va, 8);
+    } else {
+      __builtin_memcpy(cw, ua, 16);
+    }
+  } else {
+    // the last chunks of the tensor: stay inside it
+#pragma unroll
+    for (int w = 0; w < 4; ++w) yw[w] = cw[w] = 0;
+    for (int b = 0; b < 16; ++b) {
+      const uint8_t* ca = I420 ? (b < 8 ? ua + b : va + (b - 8)) : ua + b;
+      const uint32_t yb = ya + b < in_end ? ya[b] : 0u;
+      const uint32_t cb = ca < in_end ? *ca : 0u;
+      yw[b >> 2] |= yb << (8 * (b & 3));
+      cw[b >> 2] |= cb << (8 * (b & 3));
+    }
+  }
+  uint32_t o[12];
+  yuv420_convert_chunk<I420>(yw, cw, k, o);
+#pragma unroll
+  for (int v = 0; v < 3; ++v) l[v] = *reinterpret_cast<const int4*>(o + 4 * v);
+}
+
 template <typename CVT, bool NCHW, bool I420>
 __global__ void __launch_bounds__(kResizeBlock)
 yuv420_resize_normalize_kernel(
@@ -1076,36 +1112,9 @@ yuv420_resize_normalize_kernel(
         const int64_t co = int64_t(sy >> 1) * c_row + (xc >> 1) * cstep;
         const uint8_t* ua = uimg + co;
         const uint8_t* va = vimg + co;
-        uint32_t yw[4], cw[4];
-        // the V (NV12: U,V) bytes end last: if they are inside, all are
-        if ((I420 ? va + 8 : ua + 16) <= in_end && ya + 16 <= in_end) {
-          __builtin_memcpy(yw, ya, 16);
-          if constexpr (I420) {
-            __builtin_memcpy(cw, ua, 8);
-            __builtin_memcpy(cw + 2, va, 8);
-          } else {
-            __builtin_memcpy(cw, ua, 16);
-          }
-        } else {
-          // the last chunks of the tensor: stay inside it
-#pragma unroll
-          for (int w = 0; w < 4; ++w) yw[w] = cw[w] = 0;
-          for (int b = 0; b < 16; ++b) {
-            const uint8_t* ca = I420 ? (b < 8 ? ua + b : va + (b - 8))
-                                     : ua + b;
-            const uint32_t yb = ya + b < in_end ? ya[b] : 0u;
-            const uint32_t cb = ca < in_end ? *ca : 0u;
-            yw[b >> 2] |= yb << (8 * (b & 3));
-            cw[b >> 2] |= cb << (8 * (b & 3));
-          }
-        }
-        uint32_t o[12];
-        yuv420_convert_chunk<I420>(yw, cw, pp.k, o);
-        int4* l = reinterpret_cast<int4*>(
-            lds + s * p.span_stride + (xc - xe) * C);
-#pragma unroll
-        for (int v = 0; v < 3; ++v)
-          l[v] = *reinterpret_cast<const int4*>(o + 4 * v);
+        yuv420_fill_chunk<I420>(
+            ya, ua, va, in_end, pp.k,
+            reinterpret_cast<int4*>(lds + s * p.span_stride + (xc - xe) * C));
       }
       __syncthreads();
       if (active) {
@@ -1322,6 +1331,150 @@ __global__ void __launch_bounds__(kResizeAABlock) u8_resize_aa_v_kernel(
         ? out + (n * C * p.Hc + oy) * p.Wc + ox0
         : out + ((n * p.Hc + oy) * p.Wc + ox0) * C;
     resize_store_run<Out, C, NCHW>(vout, ox0, p.Wc, dst, plane);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// YUV 4:2:0 source side (NV12 / I420) of the antialiased resize + crop ingest
+// ---------------------------------------------------------------------------
+// yuv420_resize_aa_h_kernel is the horizontal pass of the recipe above on
+// frames laid out as in the bilinear YUV section: every tap is the converted,
+// clamped uint8 value of its source pixel (the int32 conversion of that
+// section, yuv_clamp8 included), widened to fp32, and the taps are walked in
+// the same ascending order with the same fmul/fadd sequence and the one
+// division by tot. It writes the fp32 workspace [n, Rs, Wc, 3] that
+// u8_resize_aa_h_kernel<3> writes for the converted frames, bit for bit; the
+// vertical pass is u8_resize_aa_v_kernel<CVT, 3, NCHW>, unchanged.
+//
+// A lane owns one (frame, source row, output column). A 256-thread workgroup
+// owns a tile of 2^tc_log2 output columns by 256 >> tc_log2 source rows (the
+// host picks the widest tile of 8..64 columns that pads Wc by at most 1/8,
+// else 8); a work item is (frame, row tile, column tile) and workgroups
+// grid-stride over work items, at most 2048 of them.
+//
+// Source taps, two paths, chosen per work item (uniform in the workgroup):
+//  * LDS path. Under the triangle filter neighbouring columns' tap ranges
+//    overlap, each source pixel feeds about two columns, and a conversion is
+//    three integer multiplies and three clamps. lo and lo + size = max(hi,
+//    lo + 1) are monotone in the output index, so every tap of the tile lies
+//    in [lo(first column), lo(last column) + size(last column)). The
+//    workgroup converts that span of each of its source rows once, from the
+//    even column xe = lo(first) & ~1 in 16-pixel chunks (yuv420_fill_chunk,
+//    as the bilinear kernel does), into LDS as RGB bytes, and the tap loops
+//    read LDS.
+//  * direct path: Yuv420Row converts each tap from global memory with byte
+//    loads. Taken when the host found that the tile's spans exceed
+//    kYuvAALdsBytes (span_px == 0: large downscale ratios) or was asked to
+//    (variant 1), or when a tile's span does not fit the host's estimate.
+constexpr int kYuvAALdsBytes = 16384;    // 10 workgroups per CU: wave-limited
+constexpr int kYuvAAMinTcLog2 = 3;       // tile: 8 columns x 32 rows ...
+constexpr int kYuvAAMaxTcLog2 = 6;       // ... to 64 columns x 4 rows
+
+struct Yuv420ResizeAAParams {
+  U8ResizeAAParams a;
+  Yuv420Coef k;
+  int tc_log2;       // output columns per tile, log2
+  int tiles_x, tiles_y;
+  int span_px;       // pixels per LDS span (multiple of 16), 0: direct
+};
+
+template <bool I420>
+__global__ void __launch_bounds__(kResizeAABlock) yuv420_resize_aa_h_kernel(
+    const uint8_t* __restrict__ in, float* __restrict__ ws, int64_t N,
+    Yuv420ResizeAAParams pp) {
+  constexpr int C = 3;
+  __shared__ __attribute__((aligned(16))) uint8_t lds[kYuvAALdsBytes];
+  const U8ResizeAAParams& p = pp.a;
+  const int tc = 1 << pp.tc_log2;                  // columns per tile
+  const int tr = kResizeAABlock >> pp.tc_log2;     // source rows per tile
+  const int r = int(threadIdx.x) >> pp.tc_log2;
+  const int j = int(threadIdx.x) & (tc - 1);
+  const int span_stride = pp.span_px * C;          // LDS bytes per row
+  const int64_t y_bytes = int64_t(p.Hin) * p.Win;
+  const int64_t c_bytes = int64_t(p.Hin >> 1) * (p.Win >> 1);   // one plane
+  const int64_t frame_bytes = y_bytes + 2 * c_bytes;
+  const int64_t c_row = I420 ? p.Win >> 1 : p.Win;   // chroma row stride
+  const int cstep = I420 ? 1 : 2;
+  const uint8_t* const in_end = in + N * frame_bytes;
+  const int64_t items = N * pp.tiles_y * pp.tiles_x;
+  for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+    const int tx = int(item % pp.tiles_x);
+    const int ty = int((item / pp.tiles_x) % pp.tiles_y);
+    const int64_t n = item / (int64_t(pp.tiles_x) * pp.tiles_y);
+    const uint8_t* img = in + n * frame_bytes;
+    const uint8_t* uimg = img + y_bytes;
+    const uint8_t* vimg = I420 ? uimg + c_bytes : uimg + 1;
+    const int s = ty * tr + r;
+    const int ox = tx * tc + j;
+    const bool active = s < p.Rs && ox < p.Wc;
+
+    // source column span of the tile, the same for every row of it
+    float unused_c;
+    int lo_f, lo_l, size_f, size_l;
+    aa_span(tx * tc + p.left, p.rw, p.sup_w, p.Win, unused_c, lo_f, size_f);
+    aa_span(min(tx * tc + tc, p.Wc) - 1 + p.left, p.rw, p.sup_w, p.Win,
+            unused_c, lo_l, size_l);
+    const int xe = lo_f & ~1;          // spans start on a chroma pair
+    const int x_end = lo_l + size_l;   // <= Win
+    // uniform in the workgroup: the barriers below are not divergent
+    const bool use_lds = pp.span_px > 0 && x_end - xe <= pp.span_px;
+
+    float c = 0.f;
+    int lo = 0, size = 0;
+    if (active) aa_span(ox + p.left, p.rw, p.sup_w, p.Win, c, lo, size);
+    float acc[C] = {0.f, 0.f, 0.f};
+    float tot = 0.f;
+
+    if (use_lds) {
+      const int nchunks = pp.span_px / kYuvChunkPx;
+      const int rows_here = min(tr, p.Rs - ty * tr);
+      const int total = rows_here * nchunks;
+      for (int idx = int(threadIdx.x); idx < total; idx += kResizeAABlock) {
+        const int fr = idx / nchunks;             // tile row
+        const int xc = xe + (idx - fr * nchunks) * kYuvChunkPx;
+        if (xc >= x_end) continue;
+        // y_base + Rs <= Hin: the row is inside the frame
+        const int sy = p.y_base + ty * tr + fr;
+        const uint8_t* ya = img + int64_t(sy) * p.Win + xc;
+        const int64_t co = int64_t(sy >> 1) * c_row + (xc >> 1) * cstep;
+        yuv420_fill_chunk<I420>(
+            ya, uimg + co, vimg + co, in_end, pp.k,
+            reinterpret_cast<int4*>(lds + fr * span_stride + (xc - xe) * C));
+      }
+      __syncthreads();
+      if (active) {
+        // xe <= lo and lo + size <= x_end (monotone in ox)
+        const uint8_t* l = lds + r * span_stride + (lo - xe) * C;
+        for (int t = 0; t < size; ++t) {
+          const float w = aa_weight(lo + t, c, p.inv_w);
+#pragma unroll
+          for (int ch = 0; ch < C; ++ch)
+            acc[ch] = __fadd_rn(acc[ch], __fmul_rn(w, float(l[t * C + ch])));
+          tot = __fadd_rn(tot, w);
+        }
+      }
+      __syncthreads();   // lds is refilled by the next work item
+    } else if (active) {
+      // lo + size <= Win and y_base + Rs <= Hin: every tap is inside the frame
+      const int sy = p.y_base + s;
+      const Yuv420Row row{img + int64_t(sy) * p.Win,
+                          uimg + int64_t(sy >> 1) * c_row,
+                          vimg + int64_t(sy >> 1) * c_row, cstep};
+      for (int t = 0; t < size; ++t) {
+        const float w = aa_weight(lo + t, c, p.inv_w);
+        float px[C];
+        row.rgb(lo + t, pp.k, px);
+#pragma unroll
+        for (int ch = 0; ch < C; ++ch)
+          acc[ch] = __fadd_rn(acc[ch], __fmul_rn(w, px[ch]));
+        tot = __fadd_rn(tot, w);
+      }
+    }
+    if (active) {
+      float* dst = ws + ((n * p.Rs + s) * p.Wc + ox) * C;   // [n][s][ox][ch]
+#pragma unroll
+      for (int ch = 0; ch < C; ++ch) dst[ch] = __fdiv_rn(acc[ch], tot);
+    }
   }
 }
 
@@ -2448,8 +2601,51 @@ at::Tensor u8_ragged_resize_normalize(
 //   (1,1080,1920,3)  -> (256,455), 224 crop   12.2 vs   72.2 vs  8.2 us
 //   (32,256,341,3)   -> (128,170)             38.0 vs  106.1 vs 10.8 us
 // The horizontal pass gathers its taps from global memory; staging the
-// source spans through LDS has not been tried, so there is no second number.
+// source spans through LDS has not been tried here, so there is no second
+// number (the YUV horizontal pass stages: see yuv420_resize_aa_normalize).
 constexpr int64_t kResizeAAWsBytes = int64_t(256) << 20;
+
+// The host side of the antialiased recipe, shared by the dense RGB and YUV
+// entries: fills `p` (normalization, ratios, support and 1/support, the crop
+// window, and the source rows y_base/Rs that the window needs) and returns
+// the images per workspace chunk under the cap (kResizeAAWsBytes, or
+// `ws_cap_bytes` when > 0; at least one image). One value per channel in
+// `scale`/`bias`.
+static int64_t resize_aa_plan(
+    U8ResizeAAParams& p, const char* who, double rh, double rw, int64_t Hin,
+    int64_t Win, int64_t top, int64_t left, int64_t Hc, int64_t Wc,
+    const std::vector<double>& scale, const std::vector<double>& bias,
+    int64_t N, int64_t ws_cap_bytes) {
+  const int64_t C = int64_t(scale.size());
+  for (int64_t c = 0; c < C; ++c) {
+    p.scale[c] = float(scale[c]);
+    p.bias[c] = float(bias[c]);
+  }
+  p.rh = float(rh);
+  p.rw = float(rw);
+  p.sup_h = p.rh >= 1.f ? p.rh : 1.f;
+  p.sup_w = p.rw >= 1.f ? p.rw : 1.f;
+  p.inv_h = p.rh >= 1.f ? float(1.0 / double(p.rh)) : 1.f;
+  p.inv_w = p.rw >= 1.f ? float(1.0 / double(p.rw)) : 1.f;
+  p.Hin = int(Hin); p.Win = int(Win);
+  p.Hc = int(Hc); p.Wc = int(Wc);
+  p.top = int(top); p.left = int(left);
+  // source rows of the crop window: [lo(first row), lo(last) + size(last))
+  float unused_c;
+  int lo_first, lo_last, size_first, size_last;
+  aa_span(p.top, p.rh, p.sup_h, p.Hin, unused_c, lo_first, size_first);
+  aa_span(p.top + p.Hc - 1, p.rh, p.sup_h, p.Hin, unused_c, lo_last,
+          size_last);
+  p.y_base = lo_first;
+  p.Rs = lo_last + size_last - lo_first;
+  TORCH_CHECK(p.Rs >= 1 && p.y_base + p.Rs <= p.Hin, who,
+              ": internal row range error");
+
+  const int64_t cap = ws_cap_bytes > 0 ? ws_cap_bytes : kResizeAAWsBytes;
+  const int64_t img_floats = int64_t(p.Rs) * Wc * C;
+  return std::max<int64_t>(
+      1, std::min<int64_t>(N, cap / (img_floats * int64_t(sizeof(float)))));
+}
 
 at::Tensor u8_nhwc_resize_aa_normalize(
     const at::Tensor& in, double rh, double rw, int64_t top, int64_t left,
@@ -2487,34 +2683,10 @@ at::Tensor u8_nhwc_resize_aa_normalize(
   if (N == 0) return out;  // zero grid: never launch
 
   U8ResizeAAParams p{};
-  for (int64_t c = 0; c < C; ++c) {
-    p.scale[c] = float(scale[c]);
-    p.bias[c] = float(bias[c]);
-  }
-  p.rh = float(rh);
-  p.rw = float(rw);
-  p.sup_h = p.rh >= 1.f ? p.rh : 1.f;
-  p.sup_w = p.rw >= 1.f ? p.rw : 1.f;
-  p.inv_h = p.rh >= 1.f ? float(1.0 / double(p.rh)) : 1.f;
-  p.inv_w = p.rw >= 1.f ? float(1.0 / double(p.rw)) : 1.f;
-  p.Hin = int(Hin); p.Win = int(Win);
-  p.Hc = int(Hc); p.Wc = int(Wc);
-  p.top = int(top); p.left = int(left);
-  // source rows of the crop window: [lo(first row), lo(last) + size(last))
-  float unused_c;
-  int lo_first, lo_last, size_first, size_last;
-  aa_span(p.top, p.rh, p.sup_h, p.Hin, unused_c, lo_first, size_first);
-  aa_span(p.top + p.Hc - 1, p.rh, p.sup_h, p.Hin, unused_c, lo_last,
-          size_last);
-  p.y_base = lo_first;
-  p.Rs = lo_last + size_last - lo_first;
-  TORCH_CHECK(p.Rs >= 1 && p.y_base + p.Rs <= p.Hin,
-              "u8_nhwc_resize_aa_normalize: internal row range error");
-
-  const int64_t cap = ws_cap_bytes > 0 ? ws_cap_bytes : kResizeAAWsBytes;
+  const int64_t chunk = resize_aa_plan(
+      p, "u8_nhwc_resize_aa_normalize", rh, rw, Hin, Win, top, left, Hc, Wc,
+      scale, bias, N, ws_cap_bytes);
   const int64_t img_floats = int64_t(p.Rs) * Wc * C;
-  const int64_t chunk = std::max<int64_t>(
-      1, std::min<int64_t>(N, cap / (img_floats * int64_t(sizeof(float)))));
   auto ws = at::empty({chunk * img_floats}, in.options().dtype(at::kFloat));
   const int64_t runs = (Wc + kResizePx - 1) / kResizePx;
   const int64_t in_img = Hin * Win * C, out_img = C * Hc * Wc;
@@ -2554,6 +2726,147 @@ at::Tensor u8_nhwc_resize_aa_normalize(
   if (out_dtype == at::kFloat) by_channels(IdF32{});
   else if (out_dtype == at::kBFloat16) by_channels(F32ToBf16{});
   else by_channels(F32ToF16{});
+  return out;
+}
+
+// YUV 4:2:0 source side of the antialiased resize + crop ingest; see the
+// kernel section. `in`, `i420` and `coef` are those of
+// yuv420_resize_normalize, the other arguments those of
+// u8_nhwc_resize_aa_normalize with C = 3; the row range, support, 1/support
+// and the workspace chunking come from resize_aa_plan, so the result is
+// bit-identical to that entry on the converted frames. `variant` 1 forces
+// the direct tap path.
+//
+// Measured on MI355X (tools/bench_yuv.py --antialias, interleaved rounds in
+// one process, median [range]), NV12, u8 -> bf16 NCHW: this entry with taps
+// from LDS vs the direct path forced vs u8_nhwc_resize_aa_normalize on the
+// already converted tensor vs ops.yuv420_to_rgb_u8 on the device followed
+// by that entry:
+//   (32,1080,1920) -> (256,455), 224 crop
+//       119.3 [117.6-122.0] vs 126.0 [125.0-127.9] vs 89.4 vs 3739.8 us
+//   (1,1080,1920)  -> (256,455), 224 crop
+//        13.2 [13.2-13.5]   vs  13.6 [13.4-14.8]   vs 12.1 vs  160.4 us
+//   (32,256,342)   -> (128,170)
+//        41.6 [41.4-43.0]   vs  40.2 [40.2-40.8]   vs 37.6 vs  197.0 us
+// The LDS path ships as the default: it is faster than the direct path on
+// both 1080p shapes (6 % and 2 %), and 3 % slower at the 2x downscale of the
+// small frames, where a column has about 4 taps. The fill keeps 80 of 256
+// lanes busy on the 1080p tile, which is where the rest of the 2x fewer
+// conversions goes; spreading a chunk over more lanes was not tried.
+at::Tensor yuv420_resize_aa_normalize(
+    const at::Tensor& in, bool i420, std::vector<int64_t> coef, double rh,
+    double rw, int64_t top, int64_t left, int64_t Hc, int64_t Wc,
+    std::vector<double> scale, std::vector<double> bias,
+    at::ScalarType out_dtype, bool out_nchw, int64_t variant,
+    int64_t ws_cap_bytes) {
+  TORCH_CHECK(in.is_cuda() && in.dim() == 3 && in.is_contiguous() &&
+              in.scalar_type() == at::kByte,
+              "yuv420_resize_aa_normalize expects a contiguous uint8 device "
+              "tensor [N,H*3/2,W]");
+  constexpr int64_t kMaxSide = 16384;
+  constexpr int64_t C = 3;
+  const int64_t N = in.size(0), Win = in.size(2);
+  TORCH_CHECK(in.size(1) % 3 == 0,
+              "yuv420_resize_aa_normalize: rows must be a multiple of 3");
+  const int64_t Hin = in.size(1) / 3 * 2;
+  TORCH_CHECK(Hin >= 2 && Hin <= kMaxSide && Win >= 2 && Win <= kMaxSide &&
+              Hin % 2 == 0 && Win % 2 == 0,
+              "yuv420_resize_aa_normalize: frame sides must be even and in "
+              "2..16384");
+  TORCH_CHECK(Hc >= 1 && Wc >= 1 && top >= 0 && left >= 0 &&
+              top + Hc <= kMaxSide && left + Wc <= kMaxSide,
+              "yuv420_resize_aa_normalize: bad crop window");
+  // a ratio is float(n_in / n_r) with both sides in 1..16384
+  TORCH_CHECK(rh > 0.0 && rw > 0.0 && rh <= double(kMaxSide) &&
+              rw <= double(kMaxSide),
+              "yuv420_resize_aa_normalize: ratios must be in (0, 16384]");
+  TORCH_CHECK(int64_t(scale.size()) == C && int64_t(bias.size()) == C,
+              "yuv420_resize_aa_normalize: scale/bias need 3 values");
+  TORCH_CHECK(coef.size() == 6,
+              "yuv420_resize_aa_normalize: coef needs 6 values");
+  for (int64_t v : coef)   // sums stay far inside int32
+    TORCH_CHECK(v >= -4096 && v <= 4096,
+                "yuv420_resize_aa_normalize: coefficient out of range");
+  TORCH_CHECK(out_dtype == at::kFloat || out_dtype == at::kBFloat16 ||
+              out_dtype == at::kHalf,
+              "yuv420_resize_aa_normalize: out_dtype must be f32, bf16 or "
+              "f16");
+  auto out = out_nchw
+      ? at::empty({N, C, Hc, Wc}, in.options().dtype(out_dtype))
+      : at::empty({N, Hc, Wc, C}, in.options().dtype(out_dtype));
+  if (N == 0) return out;  // zero grid: never launch
+
+  Yuv420ResizeAAParams pp{};
+  U8ResizeAAParams& p = pp.a;
+  const int64_t chunk = resize_aa_plan(
+      p, "yuv420_resize_aa_normalize", rh, rw, Hin, Win, top, left, Hc, Wc,
+      scale, bias, N, ws_cap_bytes);
+  pp.k = Yuv420Coef{int(coef[0]), int(coef[1]), int(coef[2]), int(coef[3]),
+                    int(coef[4]), int(coef[5])};
+  // the widest tile that pads Wc by at most 1/8, else the narrowest
+  pp.tc_log2 = kYuvAAMinTcLog2;
+  for (int l = kYuvAAMaxTcLog2; l > kYuvAAMinTcLog2; --l) {
+    const int64_t tcl = int64_t(1) << l;
+    if ((Wc + tcl - 1) / tcl * tcl - Wc <= Wc / 8) {
+      pp.tc_log2 = l;
+      break;
+    }
+  }
+  const int64_t tc = int64_t(1) << pp.tc_log2;
+  const int64_t tr = kResizeAABlock >> pp.tc_log2;
+  pp.tiles_x = int((Wc + tc - 1) / tc);
+  pp.tiles_y = int((p.Rs + tr - 1) / tr);
+  // pixels per LDS span: the widest span of a tile, (columns - 1) * rw +
+  // 2 * support + 1 rounded up with slack (an upper estimate; the kernel
+  // checks each tile's own span against it), plus one for the even start
+  // column, in whole fill chunks of 3 LDS bytes per pixel
+  const int64_t span_px = std::min<int64_t>(
+      Win, int64_t(std::ceil(double(std::min(tc, Wc)) * double(p.rw))) +
+               2 * int64_t(std::ceil(double(p.sup_w))) + 3);
+  const int64_t chunks = (span_px + 1 + kYuvChunkPx - 1) / kYuvChunkPx;
+  const bool direct =
+      variant == 1 || tr * chunks * kYuvChunkPx * C > kYuvAALdsBytes;
+  pp.span_px = direct ? 0 : int(chunks * kYuvChunkPx);
+
+  const int64_t img_floats = int64_t(p.Rs) * Wc * C;
+  auto ws = at::empty({chunk * img_floats}, in.options().dtype(at::kFloat));
+  const int64_t runs = (Wc + kResizePx - 1) / kResizePx;
+  const int64_t in_img = Hin * Win * 3 / 2, out_img = C * Hc * Wc;
+  const auto* src = static_cast<const uint8_t*>(in.const_data_ptr());
+
+  auto launch = [&](auto cvt_tag, auto nchw_tag) {
+    using CVT = decltype(cvt_tag);
+    auto* dst = reinterpret_cast<typename CVT::Out*>(out.mutable_data_ptr());
+    for (int64_t n0 = 0; n0 < N; n0 += chunk) {
+      const int64_t n = std::min(chunk, N - n0);
+      const int grid = int(std::min<int64_t>(
+          n * pp.tiles_y * pp.tiles_x, 2048));
+      if (i420)
+        hipLaunchKernelGGL(
+            (yuv420_resize_aa_h_kernel<true>), dim3(grid),
+            dim3(kResizeAABlock), 0, current_stream(), src + n0 * in_img,
+            ws.data_ptr<float>(), n, pp);
+      else
+        hipLaunchKernelGGL(
+            (yuv420_resize_aa_h_kernel<false>), dim3(grid),
+            dim3(kResizeAABlock), 0, current_stream(), src + n0 * in_img,
+            ws.data_ptr<float>(), n, pp);
+      HIP_CHECK(hipGetLastError());
+      hipLaunchKernelGGL(
+          (u8_resize_aa_v_kernel<CVT, 3, decltype(nchw_tag)::value>),
+          dim3(grid_for(n * Hc * runs, kResizeAABlock)), dim3(kResizeAABlock),
+          0, current_stream(), ws.data_ptr<float>(), dst + n0 * out_img, n,
+          p);
+      HIP_CHECK(hipGetLastError());
+    }
+  };
+  auto by_layout = [&](auto cvt_tag) {
+    if (out_nchw) launch(cvt_tag, std::true_type{});
+    else launch(cvt_tag, std::false_type{});
+  };
+  if (out_dtype == at::kFloat) by_layout(IdF32{});
+  else if (out_dtype == at::kBFloat16) by_layout(F32ToBf16{});
+  else by_layout(F32ToF16{});
   return out;
 }
 

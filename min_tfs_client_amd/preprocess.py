@@ -11,7 +11,10 @@ fused bilinear resize + crop + normalize + NCHW kernel
 selects the antialiased resize kernels for downscaled photos.
 ``Yuv420ImagePreprocess`` takes what decoders emit, NV12 or I420 frames at
 1.5 bytes per pixel, and converts them to RGB inside the same bilinear
-resize kernel (``ops.image_yuv420_resize_to_float``).
+resize kernel (``ops.image_yuv420_resize_to_float``); with ``antialias=True``
+the conversion happens inside the horizontal pass of the antialiased resize
+instead, so downscaled decoder frames get the PIL / torchvision filter
+without an RGB copy.
 ``RaggedImagePreprocess`` is the mixed-size case: one request carries N
 images of N different sizes packed back to back (``pack_ragged_images``) and
 one kernel launch (``ops.image_u8_ragged_resize_to_float``) turns them into
@@ -168,27 +171,32 @@ class Yuv420ImagePreprocess:
     normalizes in one kernel (``ops.image_yuv420_resize_to_float``; frame
     layout and ``matrix``: ``ops.yuv420_to_rgb_u8``). The result is exactly
     what :class:`ImagePreprocess` with the same arguments gives for the
-    converted RGB frames.
+    converted RGB frames, bit for bit, ``antialias=True`` included (two
+    kernels then: the horizontal pass converts, the vertical pass is the RGB
+    one).
 
     Accepts a numpy array or a torch tensor, on CPU or device. With
-    ``device`` set, the **uint8** bytes are moved there first. ``resize`` and
-    ``center_crop`` follow the rules of :class:`ImagePreprocess`, applied to
-    the frame's ``(H, W)``. Wrong dtype, rank or frame geometry raise
-    ``ValueError`` (servers answer INVALID_ARGUMENT)."""
+    ``device`` set, the **uint8** bytes are moved there first. ``resize``,
+    ``center_crop`` and ``antialias`` follow the rules of
+    :class:`ImagePreprocess`, applied to the frame's ``(H, W)``;
+    ``antialias=True`` needs ``resize`` or ``center_crop``. Wrong dtype, rank
+    or frame geometry raise ``ValueError`` (servers answer
+    INVALID_ARGUMENT)."""
 
     def __init__(self, mean, std, out_dtype=None, layout: str = "nchw",
                  pixel_scale: float = 1.0 / 255.0, device=None,
                  resize=None, center_crop=None, chroma: str = "nv12",
-                 matrix: str = "bt601"):
+                 matrix: str = "bt601", antialias: bool = False):
         self._rule = ImagePreprocess(
             mean, std, out_dtype=out_dtype, layout=layout,
             pixel_scale=pixel_scale, device=device, resize=resize,
-            center_crop=center_crop)
+            center_crop=center_crop, antialias=antialias)
         rule = self._rule
         self.mean, self.std = rule.mean, rule.std
         self.out_dtype, self.layout = rule.out_dtype, rule.layout
         self.pixel_scale, self.device = rule.pixel_scale, rule.device
         self.resize, self.center_crop = rule.resize, rule.center_crop
+        self.antialias = rule.antialias
         if len(self.mean) != 3 or len(self.std) != 3:
             raise ValueError(
                 "mean/std need 3 entries (R, G, B), got "
@@ -224,7 +232,7 @@ class Yuv420ImagePreprocess:
             x, size, self.mean, self.std, crop=self.crop_window(*size),
             out_dtype=self.out_dtype, layout=self.layout,
             pixel_scale=self.pixel_scale, chroma=self.chroma,
-            matrix=self.matrix)
+            matrix=self.matrix, antialias=self.antialias)
 
 
 class RaggedImagePreprocess:

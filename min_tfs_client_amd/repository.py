@@ -21,7 +21,10 @@ On-disk version-directory formats understood by the default loader:
                                images of N sizes in one request, or
                                "uint8_ragged_antialias": the same with the
                                antialiased filter, "nv12_resize" or
-                               "i420_resize": YUV 4:2:0 frames), "antialias"
+                               "i420_resize": YUV 4:2:0 frames, or
+                               "nv12_resize_antialias" /
+                               "i420_resize_antialias": the same with the
+                               antialiased filter), "antialias"
                                (resnet50, with "uint8_nhwc_resize"),
                                "yuv_matrix" (resnet50, with the YUV modes:
                                "bt601", "bt709" or "bt601_full"),

@@ -4,6 +4,7 @@ GPU.
 
     python tools/bench_yuv.py             # kernel/op timings, JSON lines
     python tools/bench_yuv.py --predict   # + ResNet-50 Predict p50
+    python tools/bench_yuv.py --antialias # the antialiased op instead
 
 The parent process never touches the GPU. Every step (one case of the op
 timings, the Predict comparison) runs in a fresh child process under its own
@@ -25,6 +26,14 @@ All four give the same bits (asserted). Device-event timing, warm-up then
 interleaved rounds in one process; the median round is reported with the
 range over rounds. GB/s counts the bytes that must move: the input read once
 plus the output written once.
+
+``--antialias`` times ``ops.image_yuv420_resize_to_float(...,
+antialias=True)``, u8 -> bf16 NCHW, NV12, in the same way: "yuv" (taps from
+LDS) and "yuv_direct" against "rgb", the antialiased RGB op alone on the
+already converted tensor, and "two_step", ``ops.yuv420_to_rgb_u8`` on the
+device followed by the antialiased RGB op. Shapes: (32,1080,1920) and
+(1,1080,1920) frames -> (256,455) with the 224 centre crop, and (32,256,342)
+-> (128,170). All four give the same bits (asserted).
 
 Predict p50: ``resnet50_servable("cuda:0", bf16)`` in ``nv12_resize`` mode
 with (32,384,342) frames and in ``uint8_nhwc_resize`` mode with the
@@ -54,6 +63,14 @@ for _n in (1, 32, 256):
         OP_CASES[f"n{_n}_nv12_crop224_{_short}"] = (_n, "nv12", _dt)
 OP_CASES["n32_i420_crop224_bf16"] = (32, "i420", "bfloat16")
 OP_CASES["n256_i420_crop224_bf16"] = (256, "i420", "bfloat16")
+# name -> (N, H, W, resized size, crop)
+AA_CASES = {
+    "aa_n32_1080p_256x455_crop224": (32, 1080, 1920, (256, 455),
+                                     (16, 115, 224, 224)),
+    "aa_n1_1080p_256x455_crop224": (1, 1080, 1920, (256, 455),
+                                    (16, 115, 224, 224)),
+    "aa_n32_256x342_128x170": (32, 256, 342, (128, 170), None),
+}
 STEP_TIMEOUT_S = 240
 ROUNDS = 5
 
@@ -78,10 +95,10 @@ def _stats(values):
     return {"median": v[len(v) // 2], "min": v[0], "max": v[-1]}
 
 
-def _frames(n, seed=0):
+def _frames(n, seed=0, h=HIN, w=WIN):
     import torch
     g = torch.Generator().manual_seed(seed)
-    return torch.randint(0, 256, (n, HIN * 3 // 2, WIN), dtype=torch.uint8,
+    return torch.randint(0, 256, (n, h * 3 // 2, w), dtype=torch.uint8,
                          generator=g)
 
 
@@ -138,6 +155,60 @@ def run_op_case(name):
         row["yuv_bytes"] / 1e9 / (stats["yuv"]["median"] / 1e3), 1)
     row["rgb_GB_s"] = round(
         row["rgb_bytes"] / 1e9 / (stats["rgb"]["median"] / 1e3), 1)
+    row["two_step_over_yuv"] = round(
+        stats["two_step"]["median"] / stats["yuv"]["median"], 2)
+    row["yuv_over_rgb"] = round(
+        stats["yuv"]["median"] / stats["rgb"]["median"], 2)
+    print(json.dumps(row), flush=True)
+
+
+def run_aa_case(name):
+    import torch
+
+    from min_tfs_client_amd import ops
+    from min_tfs_client_amd.preprocess import IMAGENET_MEAN, IMAGENET_STD
+
+    N, H, W, size, crop = AA_CASES[name]
+    dtype, chroma, dev = torch.bfloat16, "nv12", "cuda:0"
+    ops.require_native()
+    x = _frames(N, h=H, w=W).to(dev)
+    rgb_dev = ops.yuv420_to_rgb_u8(x, chroma)
+    reps = 50 if N > 1 else 200
+
+    def yuv(variant=0):
+        return ops.image_yuv420_resize_to_float(
+            x, size, IMAGENET_MEAN, IMAGENET_STD, crop=crop, out_dtype=dtype,
+            _variant=variant, chroma=chroma, antialias=True)
+
+    def rgb():
+        return ops.image_u8_resize_to_float(
+            rgb_dev, size, IMAGENET_MEAN, IMAGENET_STD, crop=crop,
+            out_dtype=dtype, antialias=True)
+
+    def two_step():
+        return ops.image_u8_resize_to_float(
+            ops.yuv420_to_rgb_u8(x, chroma), size, IMAGENET_MEAN,
+            IMAGENET_STD, crop=crop, out_dtype=dtype, antialias=True)
+
+    want = rgb()
+    assert torch.equal(yuv(), want) and torch.equal(yuv(1), want)
+    assert torch.equal(two_step(), want)
+    fns = {"yuv": yuv, "yuv_direct": lambda: yuv(1), "rgb": rgb,
+           "two_step": two_step}
+    rounds = {k: [] for k in fns}
+    for _ in range(ROUNDS):
+        for k, fn in fns.items():
+            rounds[k].append(time_kernel(fn, reps, 5))
+    stats = {k: _stats(v) for k, v in rounds.items()}
+    row = {"case": name, "frames": [N, H, W], "chroma": chroma,
+           "size": list(size), "crop": list(crop) if crop else None,
+           "out": "bfloat16", "antialias": True}
+    for k, st in stats.items():
+        row[f"{k}_us"] = round(st["median"] * 1e3, 2)
+        row[f"{k}_us_range"] = [round(st["min"] * 1e3, 2),
+                                round(st["max"] * 1e3, 2)]
+    row["direct_over_yuv"] = round(
+        stats["yuv_direct"]["median"] / stats["yuv"]["median"], 2)
     row["two_step_over_yuv"] = round(
         stats["two_step"]["median"] / stats["yuv"]["median"], 2)
     row["yuv_over_rgb"] = round(
@@ -207,6 +278,10 @@ def main():
     ap.add_argument("--predict", action="store_true",
                     help="also time ResNet-50 Predict, NV12 against RGB")
     ap.add_argument("--only-predict", action="store_true")
+    ap.add_argument("--antialias", action="store_true",
+                    help="time the antialiased op on its own shapes instead")
+    ap.add_argument("--aa-case", choices=sorted(AA_CASES),
+                    help="(child) run one antialiased op timing case")
     ap.add_argument("--cases", nargs="*", choices=sorted(OP_CASES),
                     help="run only these op timing cases")
     ap.add_argument("--op-case", choices=sorted(OP_CASES),
@@ -216,8 +291,14 @@ def main():
     a = ap.parse_args()
     if a.op_case:
         return run_op_case(a.op_case)
+    if a.aa_case:
+        return run_aa_case(a.aa_case)
     if a.predict_child:
         return run_predict()
+    if a.antialias:
+        for name in AA_CASES:
+            run_step(["--aa-case", name])
+        return
     if not a.only_predict:
         for name in (a.cases or OP_CASES):
             run_step(["--op-case", name])
