@@ -1230,46 +1230,143 @@ __device__ __forceinline__ float aa_weight(int i, float c, float inv) {
   return fmaxf(__fsub_rn(1.f, fabsf(x)), 0.f);
 }
 
-template <int C>
+// ---------------------------------------------------------------------------
+// the source side of the two passes: one dense tensor, or a ragged batch
+// ---------------------------------------------------------------------------
+// The output size (Hc,Wc), the lane bodies and the store path are shared by
+// the batch. The kernels' `Src` parameter says where image n lies:
+//
+//  * U8DenseAASrc: one [N,Hin,Win,C] tensor, every source field a kernel
+//    argument. The workspace is [n, Rs, Wc, C]: workspace row g belongs to
+//    image g / Rs.
+//  * U8RaggedAASrc: images back to back in one flat uint8 buffer, HWC each,
+//    no padding (taps are byte loads, so an image may start at any byte
+//    alignment). Everything on the source side is per image and comes from a
+//    table in device memory that u8_ragged_resize_aa_normalize builds. The
+//    workspace is ragged too: image i of a chunk owns Rs_i rows of Wc*C
+//    floats from workspace row ws_row0_i, the running sum of Rs over the
+//    earlier images of the same chunk (it restarts at 0 in every chunk). The
+//    horizontal pass finds the image of workspace row g by a binary search
+//    over the ws_row0 column of the chunk's table (at most 5 steps for 32
+//    images, on lines every lane of the launch shares).
+//
+// `row` sets the horizontal source fields of `q` (Win, left, rw, sup_w,
+// inv_w) for the image that owns workspace row g and returns the first byte
+// of that row's source row. `ws_row0` sets the vertical ones (Hin, top, rh,
+// sup_h, inv_h, y_base) for image n and returns its first workspace row.
+//
+// One table entry, 16 int32 words (the host fills the struct and ships the
+// table as int32 [N,16]):
+//   0-1   offset    first byte of the image in the flat buffer (int64)
+//   2-3   ws_row0   first workspace row of the image in its chunk (int64)
+//   4-7   Hin, Win, top, left
+//   8-9   rh, rw                 ratios, float32(Hin/Hr), float32(Win/Wr)
+//   10-13 sup_h, sup_w, inv_h, inv_w   as in U8ResizeAAParams
+//   14    y_base    first source row in the workspace
+//   15    Rs        source rows in the workspace (host-side chunking only)
+// Of the shared U8ResizeAAParams a ragged launch reads only scale, bias, Hc
+// and Wc.
+struct U8RaggedAAEntry {
+  int64_t offset;
+  int64_t ws_row0;
+  int Hin, Win, top, left;
+  float rh, rw;
+  float sup_h, sup_w;
+  float inv_h, inv_w;
+  int y_base, Rs;
+};
+static_assert(sizeof(U8RaggedAAEntry) == 64, "table rows are int32 [16]");
+
+struct U8DenseAASrc {
+  template <int C>
+  static __device__ __forceinline__ const uint8_t* row(
+      const uint8_t* in, const U8RaggedAAEntry*, int, int64_t g,
+      U8ResizeAAParams& q) {
+    const int s = int(g % q.Rs);
+    const int64_t n = g / q.Rs;
+    return in + (n * q.Hin + q.y_base + s) * (int64_t(q.Win) * C);
+  }
+  static __device__ __forceinline__ int64_t ws_row0(const U8RaggedAAEntry*,
+                                                    int64_t n,
+                                                    U8ResizeAAParams& q) {
+    return n * q.Rs;
+  }
+};
+
+struct U8RaggedAASrc {
+  template <int C>
+  static __device__ __forceinline__ const uint8_t* row(
+      const uint8_t* in, const U8RaggedAAEntry* table, int n_table, int64_t g,
+      U8ResizeAAParams& q) {
+    // the image whose rows hold g: the last entry with ws_row0 <= g
+    // (ws_row0 is strictly increasing, Rs >= 1, and table[0].ws_row0 == 0)
+    int first = 0, last = n_table;
+    while (last - first > 1) {
+      const int mid = (first + last) >> 1;
+      if (table[mid].ws_row0 <= g) first = mid;
+      else last = mid;
+    }
+    const U8RaggedAAEntry e = table[first];
+    q.Win = e.Win; q.left = e.left;
+    q.rw = e.rw; q.sup_w = e.sup_w; q.inv_w = e.inv_w;
+    const int s = int(g - e.ws_row0);
+    return in + e.offset + int64_t(e.y_base + s) * e.Win * C;
+  }
+  static __device__ __forceinline__ int64_t ws_row0(
+      const U8RaggedAAEntry* table, int64_t n, U8ResizeAAParams& q) {
+    const U8RaggedAAEntry e = table[n];
+    q.Hin = e.Hin; q.top = e.top;
+    q.rh = e.rh; q.sup_h = e.sup_h; q.inv_h = e.inv_h;
+    q.y_base = e.y_base;
+    return e.ws_row0;
+  }
+};
+
+// Lanes are the flattened (workspace row g, output column ox) pairs of the
+// launch's `rows` workspace rows. `table`/`n_table` (the chunk's entries) are
+// read by U8RaggedAASrc only.
+template <int C, typename Src>
 __global__ void __launch_bounds__(kResizeAABlock) u8_resize_aa_h_kernel(
-    const uint8_t* __restrict__ in, float* __restrict__ ws, int64_t N,
+    const uint8_t* __restrict__ in, float* __restrict__ ws,
+    const U8RaggedAAEntry* __restrict__ table, int n_table, int64_t rows,
     U8ResizeAAParams p) {
-  const int64_t row_bytes = int64_t(p.Win) * C;
-  const int64_t lanes = N * p.Rs * p.Wc;
+  const int64_t lanes = rows * p.Wc;
   const int64_t stride = int64_t(gridDim.x) * kResizeAABlock;
   for (int64_t idx = int64_t(blockIdx.x) * kResizeAABlock + threadIdx.x;
        idx < lanes; idx += stride) {
     const int ox = int(idx % p.Wc);
-    const int64_t t = idx / p.Wc;
-    const int s = int(t % p.Rs);
-    const int64_t n = t / p.Rs;
+    const int64_t g = idx / p.Wc;
+    U8ResizeAAParams q = p;
+    const uint8_t* row = Src::template row<C>(in, table, n_table, g, q);
     float c;
     int lo, size;
-    aa_span(ox + p.left, p.rw, p.sup_w, p.Win, c, lo, size);
+    aa_span(ox + q.left, q.rw, q.sup_w, q.Win, c, lo, size);
     // lo + size <= Win and y_base + Rs <= Hin: every tap is inside the image
-    const uint8_t* src =
-        in + (n * p.Hin + p.y_base + s) * row_bytes + int64_t(lo) * C;
+    const uint8_t* src = row + int64_t(lo) * C;
     float acc[C];
 #pragma unroll
     for (int ch = 0; ch < C; ++ch) acc[ch] = 0.f;
     float tot = 0.f;
     for (int j = 0; j < size; ++j) {
-      const float w = aa_weight(lo + j, c, p.inv_w);
+      const float w = aa_weight(lo + j, c, q.inv_w);
 #pragma unroll
       for (int ch = 0; ch < C; ++ch)
         acc[ch] = __fadd_rn(acc[ch], __fmul_rn(w, float(src[j * C + ch])));
       tot = __fadd_rn(tot, w);
     }
-    float* dst = ws + idx * C;   // [n][s][ox][ch]
+    float* dst = ws + idx * C;   // [g][ox][ch]
 #pragma unroll
     for (int ch = 0; ch < C; ++ch) dst[ch] = __fdiv_rn(acc[ch], tot);
   }
 }
 
-template <typename CVT, int C, bool NCHW>
+// Lanes are (image, oy, run of kResizePx columns). `table` is read by
+// U8RaggedAASrc only.
+template <typename CVT, int C, bool NCHW, typename Src>
 __global__ void __launch_bounds__(kResizeAABlock) u8_resize_aa_v_kernel(
     const float* __restrict__ ws, typename CVT::Out* __restrict__ out,
-    int64_t N, U8ResizeAAParams p) {
+    const U8RaggedAAEntry* __restrict__ table, int64_t N,
+    U8ResizeAAParams p) {
   using Out = typename CVT::Out;
   constexpr int L = kResizePx * C;       // floats per workspace row and lane
   static_assert(kResizePx % (16 / int(sizeof(Out))) == 0,
@@ -1285,12 +1382,13 @@ __global__ void __launch_bounds__(kResizeAABlock) u8_resize_aa_v_kernel(
     const int64_t t = idx / runs;
     const int oy = int(t % p.Hc);
     const int64_t n = t / p.Hc;
+    U8ResizeAAParams q = p;
+    const int64_t row0 = Src::ws_row0(table, n, q);
     float c;
     int lo, size;
-    aa_span(oy + p.top, p.rh, p.sup_h, p.Hin, c, lo, size);
+    aa_span(oy + q.top, q.rh, q.sup_h, q.Hin, c, lo, size);
     // y_base <= lo and lo + size <= y_base + Rs (monotone in oy)
-    const float* src =
-        ws + ((n * p.Rs + (lo - p.y_base)) * p.Wc + ox0) * C;
+    const float* src = ws + ((row0 + (lo - q.y_base)) * p.Wc + ox0) * C;
     const int valid = min(kResizePx, p.Wc - ox0) * C;   // floats of this run
     float acc[L];
 #pragma unroll
@@ -1299,12 +1397,12 @@ __global__ void __launch_bounds__(kResizeAABlock) u8_resize_aa_v_kernel(
     if (valid == L && (reinterpret_cast<uintptr_t>(src) & 15) == 0 &&
         row_floats % 4 == 0) {
       for (int j = 0; j < size; ++j, src += row_floats) {
-        const float w = aa_weight(lo + j, c, p.inv_h);
+        const float w = aa_weight(lo + j, c, q.inv_h);
         float v[L];
 #pragma unroll
-        for (int q = 0; q < L / 4; ++q)
-          reinterpret_cast<float4*>(v)[q] =
-              reinterpret_cast<const float4*>(src)[q];
+        for (int k = 0; k < L / 4; ++k)
+          reinterpret_cast<float4*>(v)[k] =
+              reinterpret_cast<const float4*>(src)[k];
 #pragma unroll
         for (int e = 0; e < L; ++e)
           acc[e] = __fadd_rn(acc[e], __fmul_rn(w, v[e]));
@@ -1312,7 +1410,7 @@ __global__ void __launch_bounds__(kResizeAABlock) u8_resize_aa_v_kernel(
       }
     } else {
       for (int j = 0; j < size; ++j, src += row_floats) {
-        const float w = aa_weight(lo + j, c, p.inv_h);
+        const float w = aa_weight(lo + j, c, q.inv_h);
 #pragma unroll
         for (int e = 0; e < L; ++e)
           acc[e] = __fadd_rn(acc[e], __fmul_rn(w, src[min(e, valid - 1)]));
@@ -1344,7 +1442,7 @@ __global__ void __launch_bounds__(kResizeAABlock) u8_resize_aa_v_kernel(
 // the same ascending order with the same fmul/fadd sequence and the one
 // division by tot. It writes the fp32 workspace [n, Rs, Wc, 3] that
 // u8_resize_aa_h_kernel<3> writes for the converted frames, bit for bit; the
-// vertical pass is u8_resize_aa_v_kernel<CVT, 3, NCHW>, unchanged.
+// vertical pass is u8_resize_aa_v_kernel<CVT, 3, NCHW, U8DenseAASrc>.
 //
 // A lane owns one (frame, source row, output column). A 256-thread workgroup
 // owns a tile of 2^tc_log2 output columns by 256 >> tc_log2 source rows (the
@@ -1475,167 +1573,6 @@ __global__ void __launch_bounds__(kResizeAABlock) yuv420_resize_aa_h_kernel(
 #pragma unroll
       for (int ch = 0; ch < C; ++ch) dst[ch] = __fdiv_rn(acc[ch], tot);
     }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// antialiased ragged batch: N images of N different sizes, two launches
-// ---------------------------------------------------------------------------
-// The antialiased recipe above, bit for bit (aa_span, aa_weight and
-// resize_store_run are shared, the lane bodies are those of the two dense
-// kernels), for images that lie back to back in one flat uint8 buffer, HWC
-// each, no padding, as in the bilinear ragged section. The output size
-// (Hc,Wc) is shared; everything on the source side is per image and comes
-// from a table in device memory that u8_ragged_resize_aa_normalize builds.
-//
-// The fp32 workspace is ragged too: image i of a chunk owns Rs_i rows of
-// Wc*C floats from workspace row ws_row0_i, the running sum of Rs over the
-// earlier images of the same chunk (it restarts at 0 in every chunk).
-//
-//  1. u8_ragged_resize_aa_h_kernel: lanes are the flattened (workspace row
-//     g, output column ox) pairs of the chunk. A lane finds its image by a
-//     binary search for g over the ws_row0 column of the chunk's table (at
-//     most 5 steps for 32 images, on lines every lane of the launch shares),
-//     then does what the dense horizontal lane does for (image, y_base_i +
-//     g - ws_row0_i, ox). Its taps are byte loads, so an image may start at
-//     any byte alignment.
-//  2. u8_ragged_resize_aa_v_kernel: lanes are (image, oy, run of kResizePx
-//     columns) as in the dense vertical kernel; the image's rows start at
-//     workspace row ws_row0_n and its ratio, support and crop origin come
-//     from the table. Both load paths and the stores are the dense kernel's.
-//
-// One table entry, 16 int32 words (the host fills the struct and ships the
-// table as int32 [N,16]):
-//   0-1   offset    first byte of the image in the flat buffer (int64)
-//   2-3   ws_row0   first workspace row of the image in its chunk (int64)
-//   4-7   Hin, Win, top, left
-//   8-9   rh, rw                 ratios, float32(Hin/Hr), float32(Win/Wr)
-//   10-13 sup_h, sup_w, inv_h, inv_w   as in U8ResizeAAParams
-//   14    y_base    first source row in the workspace
-//   15    Rs        source rows in the workspace (host-side chunking only)
-// Of the shared U8ResizeAAParams only scale, bias, Hc and Wc are read.
-struct U8RaggedAAEntry {
-  int64_t offset;
-  int64_t ws_row0;
-  int Hin, Win, top, left;
-  float rh, rw;
-  float sup_h, sup_w;
-  float inv_h, inv_w;
-  int y_base, Rs;
-};
-static_assert(sizeof(U8RaggedAAEntry) == 64, "table rows are int32 [16]");
-
-template <int C>
-__global__ void __launch_bounds__(kResizeAABlock) u8_ragged_resize_aa_h_kernel(
-    const uint8_t* __restrict__ in, float* __restrict__ ws,
-    const U8RaggedAAEntry* __restrict__ table, int N, int64_t rows,
-    U8ResizeAAParams p) {
-  const int64_t lanes = rows * p.Wc;
-  const int64_t stride = int64_t(gridDim.x) * kResizeAABlock;
-  for (int64_t idx = int64_t(blockIdx.x) * kResizeAABlock + threadIdx.x;
-       idx < lanes; idx += stride) {
-    const int ox = int(idx % p.Wc);
-    const int64_t g = idx / p.Wc;
-    // the image whose rows hold g: the last entry with ws_row0 <= g
-    // (ws_row0 is strictly increasing, Rs >= 1, and table[0].ws_row0 == 0)
-    int first = 0, last = N;
-    while (last - first > 1) {
-      const int mid = (first + last) >> 1;
-      if (table[mid].ws_row0 <= g) first = mid;
-      else last = mid;
-    }
-    const U8RaggedAAEntry e = table[first];
-    const int s = int(g - e.ws_row0);
-    float c;
-    int lo, size;
-    aa_span(ox + e.left, e.rw, e.sup_w, e.Win, c, lo, size);
-    // lo + size <= Win and y_base + Rs <= Hin: every tap is inside the image
-    const uint8_t* src = in + e.offset +
-        (int64_t(e.y_base + s) * e.Win + lo) * C;
-    float acc[C];
-#pragma unroll
-    for (int ch = 0; ch < C; ++ch) acc[ch] = 0.f;
-    float tot = 0.f;
-    for (int j = 0; j < size; ++j) {
-      const float w = aa_weight(lo + j, c, e.inv_w);
-#pragma unroll
-      for (int ch = 0; ch < C; ++ch)
-        acc[ch] = __fadd_rn(acc[ch], __fmul_rn(w, float(src[j * C + ch])));
-      tot = __fadd_rn(tot, w);
-    }
-    float* dst = ws + idx * C;   // [g][ox][ch]
-#pragma unroll
-    for (int ch = 0; ch < C; ++ch) dst[ch] = __fdiv_rn(acc[ch], tot);
-  }
-}
-
-template <typename CVT, int C, bool NCHW>
-__global__ void __launch_bounds__(kResizeAABlock) u8_ragged_resize_aa_v_kernel(
-    const float* __restrict__ ws, typename CVT::Out* __restrict__ out,
-    const U8RaggedAAEntry* __restrict__ table, int64_t N,
-    U8ResizeAAParams p) {
-  using Out = typename CVT::Out;
-  constexpr int L = kResizePx * C;       // floats per workspace row and lane
-  static_assert(kResizePx % (16 / int(sizeof(Out))) == 0,
-                "a lane run must fill whole 16 B stores");
-  const int runs = (p.Wc + kResizePx - 1) / kResizePx;
-  const int64_t plane = int64_t(p.Hc) * p.Wc;
-  const int64_t row_floats = int64_t(p.Wc) * C;
-  const int64_t lanes = N * p.Hc * runs;
-  const int64_t stride = int64_t(gridDim.x) * kResizeAABlock;
-  for (int64_t idx = int64_t(blockIdx.x) * kResizeAABlock + threadIdx.x;
-       idx < lanes; idx += stride) {
-    const int ox0 = int(idx % runs) * kResizePx;
-    const int64_t t = idx / runs;
-    const int oy = int(t % p.Hc);
-    const int64_t n = t / p.Hc;
-    const U8RaggedAAEntry e = table[n];
-    float c;
-    int lo, size;
-    aa_span(oy + e.top, e.rh, e.sup_h, e.Hin, c, lo, size);
-    // y_base <= lo and lo + size <= y_base + Rs (monotone in oy)
-    const float* src =
-        ws + ((e.ws_row0 + (lo - e.y_base)) * p.Wc + ox0) * C;
-    const int valid = min(kResizePx, p.Wc - ox0) * C;   // floats of this run
-    float acc[L];
-#pragma unroll
-    for (int k = 0; k < L; ++k) acc[k] = 0.f;
-    float tot = 0.f;
-    if (valid == L && (reinterpret_cast<uintptr_t>(src) & 15) == 0 &&
-        row_floats % 4 == 0) {
-      for (int j = 0; j < size; ++j, src += row_floats) {
-        const float w = aa_weight(lo + j, c, e.inv_h);
-        float v[L];
-#pragma unroll
-        for (int q = 0; q < L / 4; ++q)
-          reinterpret_cast<float4*>(v)[q] =
-              reinterpret_cast<const float4*>(src)[q];
-#pragma unroll
-        for (int k = 0; k < L; ++k)
-          acc[k] = __fadd_rn(acc[k], __fmul_rn(w, v[k]));
-        tot = __fadd_rn(tot, w);
-      }
-    } else {
-      for (int j = 0; j < size; ++j, src += row_floats) {
-        const float w = aa_weight(lo + j, c, e.inv_h);
-#pragma unroll
-        for (int k = 0; k < L; ++k)
-          acc[k] = __fadd_rn(acc[k], __fmul_rn(w, src[min(k, valid - 1)]));
-        tot = __fadd_rn(tot, w);
-      }
-    }
-    Out vout[L];   // NCHW: [c][k], NHWC: [k][c]
-#pragma unroll
-    for (int k = 0; k < kResizePx; ++k)
-#pragma unroll
-      for (int ch = 0; ch < C; ++ch)
-        vout[NCHW ? ch * kResizePx + k : k * C + ch] = CVT::cvt(__fadd_rn(
-            __fmul_rn(__fdiv_rn(acc[k * C + ch], tot), p.scale[ch]),
-            p.bias[ch]));
-    Out* dst = NCHW
-        ? out + (n * C * p.Hc + oy) * p.Wc + ox0
-        : out + ((n * p.Hc + oy) * p.Wc + ox0) * C;
-    resize_store_run<Out, C, NCHW>(vout, ox0, p.Wc, dst, plane);
   }
 }
 
@@ -2196,6 +2133,79 @@ at::Tensor nhwc_to_nchw(const at::Tensor& in, at::ScalarType out_dtype) {
   return out;
 }
 
+// --- shared by the image ingest entries below ---
+
+// Calls f(CVT tag, integral_constant<int, C>, bool_constant<NCHW>) for a
+// call's out dtype (validated by check_out_dtype), channel count (1..4)
+// and layout.
+template <typename F>
+static void dispatch_image_out(at::ScalarType out_dtype, int64_t C,
+                               bool out_nchw, F&& f) {
+  auto by_layout = [&](auto cvt_tag, auto c_tag) {
+    if (out_nchw) f(cvt_tag, c_tag, std::true_type{});
+    else f(cvt_tag, c_tag, std::false_type{});
+  };
+  auto by_channels = [&](auto cvt_tag) {
+    switch (C) {
+      case 1: by_layout(cvt_tag, std::integral_constant<int, 1>{}); break;
+      case 2: by_layout(cvt_tag, std::integral_constant<int, 2>{}); break;
+      case 3: by_layout(cvt_tag, std::integral_constant<int, 3>{}); break;
+      default: by_layout(cvt_tag, std::integral_constant<int, 4>{});
+    }
+  };
+  if (out_dtype == at::kFloat) by_channels(IdF32{});
+  else if (out_dtype == at::kBFloat16) by_channels(F32ToBf16{});
+  else by_channels(F32ToF16{});
+}
+
+// `count` words the message: "one value per channel", "3 values".
+static void check_scale_bias(const char* who, const std::vector<double>& scale,
+                             const std::vector<double>& bias, int64_t C,
+                             const char* count) {
+  TORCH_CHECK(int64_t(scale.size()) == C && int64_t(bias.size()) == C, who,
+              ": scale/bias need ", count);
+}
+
+static void check_out_dtype(const char* who, at::ScalarType out_dtype) {
+  TORCH_CHECK(out_dtype == at::kFloat || out_dtype == at::kBFloat16 ||
+              out_dtype == at::kHalf,
+              who, ": out_dtype must be f32, bf16 or f16");
+}
+
+static at::Tensor image_out(const at::Tensor& in, int64_t N, int64_t C,
+                            int64_t Hc, int64_t Wc, at::ScalarType out_dtype,
+                            bool out_nchw) {
+  return out_nchw
+      ? at::empty({N, C, Hc, Wc}, in.options().dtype(out_dtype))
+      : at::empty({N, Hc, Wc, C}, in.options().dtype(out_dtype));
+}
+
+template <typename P>
+static void fill_scale_bias(P& p, const std::vector<double>& scale,
+                            const std::vector<double>& bias) {
+  for (size_t c = 0; c < scale.size(); ++c) {
+    p.scale[c] = float(scale[c]);
+    p.bias[c] = float(bias[c]);
+  }
+}
+
+// Tile geometry of the bilinear kernels, from the output size: the narrowest
+// power-of-two count of lane runs that covers a row, within 8..32 runs
+// (64..256 columns, 32..8 rows). Fills twl_log2, tiles_x and tiles_y.
+struct ResizeTile { int64_t tw, tr; };   // columns and rows per tile
+static ResizeTile resize_tile_geometry(U8ResizeParams& p, int64_t Hc,
+                                       int64_t Wc) {
+  const int64_t runs = (Wc + kResizePx - 1) / kResizePx;
+  p.twl_log2 = kResizeMinTwlLog2;
+  while (p.twl_log2 < kResizeMaxTwlLog2 && (int64_t(1) << p.twl_log2) < runs)
+    ++p.twl_log2;
+  const int64_t tw = (int64_t(1) << p.twl_log2) * kResizePx;
+  const int64_t tr = kResizeBlock >> p.twl_log2;
+  p.tiles_x = int((Wc + tw - 1) / tw);
+  p.tiles_y = int((Hc + tr - 1) / tr);
+  return {tw, tr};
+}
+
 // Fused uint8 NHWC image ingest: dequantize + per-channel normalize, out in
 // f32/bf16/f16, NCHW or NHWC. `scale`/`bias` hold one value per channel,
 // already rounded to fp32 by the caller (ops.normalization_constants).
@@ -2209,22 +2219,15 @@ at::Tensor u8_nhwc_normalize(const at::Tensor& in, std::vector<double> scale,
   const int64_t N = in.size(0), H = in.size(1), W = in.size(2),
                 C = in.size(3);
   TORCH_CHECK(C >= 1 && C <= 4, "u8_nhwc_normalize: C must be in 1..4");
-  TORCH_CHECK(int64_t(scale.size()) == C && int64_t(bias.size()) == C,
-              "u8_nhwc_normalize: scale/bias need one value per channel");
-  TORCH_CHECK(out_dtype == at::kFloat || out_dtype == at::kBFloat16 ||
-              out_dtype == at::kHalf,
-              "u8_nhwc_normalize: out_dtype must be f32, bf16 or f16");
+  check_scale_bias("u8_nhwc_normalize", scale, bias, C,
+                   "one value per channel");
+  check_out_dtype("u8_nhwc_normalize", out_dtype);
   const int64_t HW = H * W;
-  auto out = out_nchw
-      ? at::empty({N, C, H, W}, in.options().dtype(out_dtype))
-      : at::empty({N, H, W, C}, in.options().dtype(out_dtype));
+  auto out = image_out(in, N, C, H, W, out_dtype, out_nchw);
   if (N * HW == 0) return out;  // grid_for(0) is a zero grid: never launch
 
   U8NormParams p{};
-  for (int64_t c = 0; c < C; ++c) {
-    p.scale[c] = float(scale[c]);
-    p.bias[c] = float(bias[c]);
-  }
+  fill_scale_bias(p, scale, bias);
   // pixels per lane: 8 (C=3: 24 B/lane as 3x 8 B loads) measured FASTER
   // than 16 (3x 16 B loads) on MI355X, interleaved rounds in one process,
   // u8 NHWC -> NCHW:  (32,224,224,3)  f32 6.9 vs 9.7 us, bf16 5.0 vs 5.2 us;
@@ -2236,7 +2239,8 @@ at::Tensor u8_nhwc_normalize(const at::Tensor& in, std::vector<double> scale,
   const int grid = grid_for(N * ((HW + HWPL - 1) / HWPL), block);
   const auto* src = static_cast<const uint8_t*>(in.const_data_ptr());
 
-  auto launch = [&](auto cvt_tag, auto c_tag, auto nchw_tag) {
+  dispatch_image_out(out_dtype, C, out_nchw,
+                     [&](auto cvt_tag, auto c_tag, auto nchw_tag) {
     using CVT = decltype(cvt_tag);
     hipLaunchKernelGGL(
         (u8_nhwc_normalize_kernel<CVT, decltype(c_tag)::value, HWPL,
@@ -2244,22 +2248,7 @@ at::Tensor u8_nhwc_normalize(const at::Tensor& in, std::vector<double> scale,
         dim3(grid), dim3(block), 0, current_stream(), src,
         reinterpret_cast<typename CVT::Out*>(out.mutable_data_ptr()), HW, N,
         p);
-  };
-  auto by_layout = [&](auto cvt_tag, auto c_tag) {
-    if (out_nchw) launch(cvt_tag, c_tag, std::true_type{});
-    else launch(cvt_tag, c_tag, std::false_type{});
-  };
-  auto by_channels = [&](auto cvt_tag) {
-    switch (C) {
-      case 1: by_layout(cvt_tag, std::integral_constant<int, 1>{}); break;
-      case 2: by_layout(cvt_tag, std::integral_constant<int, 2>{}); break;
-      case 3: by_layout(cvt_tag, std::integral_constant<int, 3>{}); break;
-      default: by_layout(cvt_tag, std::integral_constant<int, 4>{});
-    }
-  };
-  if (out_dtype == at::kFloat) by_channels(IdF32{});
-  else if (out_dtype == at::kBFloat16) by_channels(F32ToBf16{});
-  else by_channels(F32ToF16{});
+  });
   HIP_CHECK(hipGetLastError());
   return out;
 }
@@ -2290,37 +2279,20 @@ at::Tensor u8_nhwc_resize_normalize(
               "u8_nhwc_resize_normalize: bad crop window");
   TORCH_CHECK(rh > 0.0 && rw > 0.0,
               "u8_nhwc_resize_normalize: ratios must be positive");
-  TORCH_CHECK(int64_t(scale.size()) == C && int64_t(bias.size()) == C,
-              "u8_nhwc_resize_normalize: scale/bias need one value per "
-              "channel");
-  TORCH_CHECK(out_dtype == at::kFloat || out_dtype == at::kBFloat16 ||
-              out_dtype == at::kHalf,
-              "u8_nhwc_resize_normalize: out_dtype must be f32, bf16 or f16");
-  auto out = out_nchw
-      ? at::empty({N, C, Hc, Wc}, in.options().dtype(out_dtype))
-      : at::empty({N, Hc, Wc, C}, in.options().dtype(out_dtype));
+  check_scale_bias("u8_nhwc_resize_normalize", scale, bias, C,
+                   "one value per channel");
+  check_out_dtype("u8_nhwc_resize_normalize", out_dtype);
+  auto out = image_out(in, N, C, Hc, Wc, out_dtype, out_nchw);
   if (N == 0) return out;  // zero grid: never launch
 
   U8ResizeParams p{};
-  for (int64_t c = 0; c < C; ++c) {
-    p.scale[c] = float(scale[c]);
-    p.bias[c] = float(bias[c]);
-  }
+  fill_scale_bias(p, scale, bias);
   p.rh = float(rh);
   p.rw = float(rw);
   p.Hin = int(Hin); p.Win = int(Win);
   p.Hc = int(Hc); p.Wc = int(Wc);
   p.top = int(top); p.left = int(left);
-  // tile: the narrowest power-of-two count of lane runs that covers a row,
-  // within 8..32 runs (64..256 columns, 32..8 rows)
-  const int64_t runs = (Wc + kResizePx - 1) / kResizePx;
-  p.twl_log2 = kResizeMinTwlLog2;
-  while (p.twl_log2 < kResizeMaxTwlLog2 && (int64_t(1) << p.twl_log2) < runs)
-    ++p.twl_log2;
-  const int64_t tw = (int64_t(1) << p.twl_log2) * kResizePx;
-  const int64_t tr = kResizeBlock >> p.twl_log2;
-  p.tiles_x = int((Wc + tw - 1) / tw);
-  p.tiles_y = int((Hc + tr - 1) / tr);
+  const auto [tw, tr] = resize_tile_geometry(p, Hc, Wc);
   // LDS bytes per source-row span: the widest span of a tile (an upper
   // estimate; the kernel checks each tile's own span against it) plus up to
   // 15 bytes of misalignment, in whole 16 B chunks
@@ -2343,29 +2315,15 @@ at::Tensor u8_nhwc_resize_normalize(
   const int grid = int(std::min<int64_t>(items, 2048));
   const auto* src = static_cast<const uint8_t*>(in.const_data_ptr());
 
-  auto launch = [&](auto cvt_tag, auto c_tag, auto nchw_tag) {
+  dispatch_image_out(out_dtype, C, out_nchw,
+                     [&](auto cvt_tag, auto c_tag, auto nchw_tag) {
     using CVT = decltype(cvt_tag);
     hipLaunchKernelGGL(
         (u8_nhwc_resize_normalize_kernel<CVT, decltype(c_tag)::value,
                                          decltype(nchw_tag)::value>),
         dim3(grid), dim3(kResizeBlock), 0, current_stream(), src,
         reinterpret_cast<typename CVT::Out*>(out.mutable_data_ptr()), N, p);
-  };
-  auto by_layout = [&](auto cvt_tag, auto c_tag) {
-    if (out_nchw) launch(cvt_tag, c_tag, std::true_type{});
-    else launch(cvt_tag, c_tag, std::false_type{});
-  };
-  auto by_channels = [&](auto cvt_tag) {
-    switch (C) {
-      case 1: by_layout(cvt_tag, std::integral_constant<int, 1>{}); break;
-      case 2: by_layout(cvt_tag, std::integral_constant<int, 2>{}); break;
-      case 3: by_layout(cvt_tag, std::integral_constant<int, 3>{}); break;
-      default: by_layout(cvt_tag, std::integral_constant<int, 4>{});
-    }
-  };
-  if (out_dtype == at::kFloat) by_channels(IdF32{});
-  else if (out_dtype == at::kBFloat16) by_channels(F32ToBf16{});
-  else by_channels(F32ToF16{});
+  });
   HIP_CHECK(hipGetLastError());
   return out;
 }
@@ -2400,27 +2358,19 @@ at::Tensor yuv420_resize_normalize(
               "yuv420_resize_normalize: bad crop window");
   TORCH_CHECK(rh > 0.0 && rw > 0.0,
               "yuv420_resize_normalize: ratios must be positive");
-  TORCH_CHECK(int64_t(scale.size()) == C && int64_t(bias.size()) == C,
-              "yuv420_resize_normalize: scale/bias need 3 values");
+  check_scale_bias("yuv420_resize_normalize", scale, bias, C, "3 values");
   TORCH_CHECK(coef.size() == 6,
               "yuv420_resize_normalize: coef needs 6 values");
   for (int64_t v : coef)   // sums stay far inside int32
     TORCH_CHECK(v >= -4096 && v <= 4096,
                 "yuv420_resize_normalize: coefficient out of range");
-  TORCH_CHECK(out_dtype == at::kFloat || out_dtype == at::kBFloat16 ||
-              out_dtype == at::kHalf,
-              "yuv420_resize_normalize: out_dtype must be f32, bf16 or f16");
-  auto out = out_nchw
-      ? at::empty({N, C, Hc, Wc}, in.options().dtype(out_dtype))
-      : at::empty({N, Hc, Wc, C}, in.options().dtype(out_dtype));
+  check_out_dtype("yuv420_resize_normalize", out_dtype);
+  auto out = image_out(in, N, C, Hc, Wc, out_dtype, out_nchw);
   if (N == 0) return out;  // zero grid: never launch
 
   Yuv420ResizeParams pp{};
   U8ResizeParams& p = pp.r;
-  for (int64_t c = 0; c < C; ++c) {
-    p.scale[c] = float(scale[c]);
-    p.bias[c] = float(bias[c]);
-  }
+  fill_scale_bias(p, scale, bias);
   pp.k = Yuv420Coef{int(coef[0]), int(coef[1]), int(coef[2]), int(coef[3]),
                     int(coef[4]), int(coef[5])};
   p.rh = float(rh);
@@ -2428,15 +2378,7 @@ at::Tensor yuv420_resize_normalize(
   p.Hin = int(Hin); p.Win = int(Win);
   p.Hc = int(Hc); p.Wc = int(Wc);
   p.top = int(top); p.left = int(left);
-  // tile geometry from Wc, as in u8_nhwc_resize_normalize
-  const int64_t runs = (Wc + kResizePx - 1) / kResizePx;
-  p.twl_log2 = kResizeMinTwlLog2;
-  while (p.twl_log2 < kResizeMaxTwlLog2 && (int64_t(1) << p.twl_log2) < runs)
-    ++p.twl_log2;
-  const int64_t tw = (int64_t(1) << p.twl_log2) * kResizePx;
-  const int64_t tr = kResizeBlock >> p.twl_log2;
-  p.tiles_x = int((Wc + tw - 1) / tw);
-  p.tiles_y = int((Hc + tr - 1) / tr);
+  const auto [tw, tr] = resize_tile_geometry(p, Hc, Wc);
   // pixels per LDS span: the widest span of a tile (an upper estimate; the
   // kernel checks each tile's own span against it) plus one for the even
   // start column, in whole fill chunks of 3 LDS bytes per pixel
@@ -2453,25 +2395,21 @@ at::Tensor yuv420_resize_normalize(
   const int grid = int(std::min<int64_t>(items, 2048));
   const auto* src = static_cast<const uint8_t*>(in.const_data_ptr());
 
-  auto launch = [&](auto cvt_tag, auto nchw_tag, auto i420_tag) {
+  // C is 3: the channel tag is not used
+  dispatch_image_out(out_dtype, C, out_nchw,
+                     [&](auto cvt_tag, auto, auto nchw_tag) {
     using CVT = decltype(cvt_tag);
-    hipLaunchKernelGGL(
-        (yuv420_resize_normalize_kernel<CVT, decltype(nchw_tag)::value,
-                                        decltype(i420_tag)::value>),
-        dim3(grid), dim3(kResizeBlock), 0, current_stream(), src,
-        reinterpret_cast<typename CVT::Out*>(out.mutable_data_ptr()), N, pp);
-  };
-  auto by_chroma = [&](auto cvt_tag, auto nchw_tag) {
-    if (i420) launch(cvt_tag, nchw_tag, std::true_type{});
-    else launch(cvt_tag, nchw_tag, std::false_type{});
-  };
-  auto by_layout = [&](auto cvt_tag) {
-    if (out_nchw) by_chroma(cvt_tag, std::true_type{});
-    else by_chroma(cvt_tag, std::false_type{});
-  };
-  if (out_dtype == at::kFloat) by_layout(IdF32{});
-  else if (out_dtype == at::kBFloat16) by_layout(F32ToBf16{});
-  else by_layout(F32ToF16{});
+    auto launch = [&](auto i420_tag) {
+      hipLaunchKernelGGL(
+          (yuv420_resize_normalize_kernel<CVT, decltype(nchw_tag)::value,
+                                          decltype(i420_tag)::value>),
+          dim3(grid), dim3(kResizeBlock), 0, current_stream(), src,
+          reinterpret_cast<typename CVT::Out*>(out.mutable_data_ptr()), N,
+          pp);
+    };
+    if (i420) launch(std::true_type{});
+    else launch(std::false_type{});
+  });
   HIP_CHECK(hipGetLastError());
   return out;
 }
@@ -2520,34 +2458,17 @@ at::Tensor u8_ragged_resize_normalize(
               "u8_ragged_resize_normalize: C must be in 1..4");
   TORCH_CHECK(Hc >= 1 && Wc >= 1 && Hc <= kMaxSide && Wc <= kMaxSide,
               "u8_ragged_resize_normalize: bad output size");
-  TORCH_CHECK(int64_t(scale.size()) == C && int64_t(bias.size()) == C,
-              "u8_ragged_resize_normalize: scale/bias need one value per "
-              "channel");
-  TORCH_CHECK(out_dtype == at::kFloat || out_dtype == at::kBFloat16 ||
-              out_dtype == at::kHalf,
-              "u8_ragged_resize_normalize: out_dtype must be f32, bf16 or "
-              "f16");
+  check_scale_bias("u8_ragged_resize_normalize", scale, bias, C,
+                   "one value per channel");
+  check_out_dtype("u8_ragged_resize_normalize", out_dtype);
   const int64_t N = table.size(0);
-  auto out = out_nchw
-      ? at::empty({N, C, Hc, Wc}, in.options().dtype(out_dtype))
-      : at::empty({N, Hc, Wc, C}, in.options().dtype(out_dtype));
+  auto out = image_out(in, N, C, Hc, Wc, out_dtype, out_nchw);
   if (N == 0) return out;  // zero grid: never launch
 
   U8ResizeParams p{};      // the source-side fields come from the table
-  for (int64_t c = 0; c < C; ++c) {
-    p.scale[c] = float(scale[c]);
-    p.bias[c] = float(bias[c]);
-  }
+  fill_scale_bias(p, scale, bias);
   p.Hc = int(Hc); p.Wc = int(Wc);
-  // tile geometry from Wc, as in u8_nhwc_resize_normalize
-  const int64_t runs = (Wc + kResizePx - 1) / kResizePx;
-  p.twl_log2 = kResizeMinTwlLog2;
-  while (p.twl_log2 < kResizeMaxTwlLog2 && (int64_t(1) << p.twl_log2) < runs)
-    ++p.twl_log2;
-  const int64_t tw = (int64_t(1) << p.twl_log2) * kResizePx;
-  const int64_t tr = kResizeBlock >> p.twl_log2;
-  p.tiles_x = int((Wc + tw - 1) / tw);
-  p.tiles_y = int((Hc + tr - 1) / tr);
+  resize_tile_geometry(p, Hc, Wc);
 
   const int64_t items = N * p.tiles_y * p.tiles_x;
   const int grid = int(std::min<int64_t>(items, 2048));
@@ -2555,7 +2476,8 @@ at::Tensor u8_ragged_resize_normalize(
   const auto* tab = static_cast<const U8RaggedEntry*>(table.const_data_ptr());
   const int64_t in_bytes = in.numel();
 
-  auto launch = [&](auto cvt_tag, auto c_tag, auto nchw_tag) {
+  dispatch_image_out(out_dtype, C, out_nchw,
+                     [&](auto cvt_tag, auto c_tag, auto nchw_tag) {
     using CVT = decltype(cvt_tag);
     hipLaunchKernelGGL(
         (u8_ragged_resize_normalize_kernel<CVT, decltype(c_tag)::value,
@@ -2563,22 +2485,7 @@ at::Tensor u8_ragged_resize_normalize(
         dim3(grid), dim3(kResizeBlock), 0, current_stream(), src, in_bytes,
         tab, reinterpret_cast<typename CVT::Out*>(out.mutable_data_ptr()), N,
         p);
-  };
-  auto by_layout = [&](auto cvt_tag, auto c_tag) {
-    if (out_nchw) launch(cvt_tag, c_tag, std::true_type{});
-    else launch(cvt_tag, c_tag, std::false_type{});
-  };
-  auto by_channels = [&](auto cvt_tag) {
-    switch (C) {
-      case 1: by_layout(cvt_tag, std::integral_constant<int, 1>{}); break;
-      case 2: by_layout(cvt_tag, std::integral_constant<int, 2>{}); break;
-      case 3: by_layout(cvt_tag, std::integral_constant<int, 3>{}); break;
-      default: by_layout(cvt_tag, std::integral_constant<int, 4>{});
-    }
-  };
-  if (out_dtype == at::kFloat) by_channels(IdF32{});
-  else if (out_dtype == at::kBFloat16) by_channels(F32ToBf16{});
-  else by_channels(F32ToF16{});
+  });
   HIP_CHECK(hipGetLastError());
   return out;
 }
@@ -2605,6 +2512,29 @@ at::Tensor u8_ragged_resize_normalize(
 // number (the YUV horizontal pass stages: see yuv420_resize_aa_normalize).
 constexpr int64_t kResizeAAWsBytes = int64_t(256) << 20;
 
+// One axis of the antialiased recipe on the host, shared by the dense plan
+// and the per-image loop of the ragged plan, so both give the kernels the
+// same numbers: the filter support and 1/support of a ratio ...
+static void aa_support(float r, float& support, float& inv) {
+  support = r >= 1.f ? r : 1.f;
+  inv = r >= 1.f ? float(1.0 / double(r)) : 1.f;
+}
+
+// ... and the source rows one crop window needs, [lo(first row), lo(last) +
+// size(last)). `who` is the prefix of the error message, in pieces.
+template <typename... Who>
+static void aa_row_range(int top, int Hc, float rh, float sup_h, int Hin,
+                         int& y_base, int& Rs, const Who&... who) {
+  float unused_c;
+  int lo_first, lo_last, size_first, size_last;
+  aa_span(top, rh, sup_h, Hin, unused_c, lo_first, size_first);
+  aa_span(top + Hc - 1, rh, sup_h, Hin, unused_c, lo_last, size_last);
+  y_base = lo_first;
+  Rs = lo_last + size_last - lo_first;
+  TORCH_CHECK(Rs >= 1 && y_base + Rs <= Hin, who...,
+              ": internal row range error");
+}
+
 // The host side of the antialiased recipe, shared by the dense RGB and YUV
 // entries: fills `p` (normalization, ratios, support and 1/support, the crop
 // window, and the source rows y_base/Rs that the window needs) and returns
@@ -2617,29 +2547,15 @@ static int64_t resize_aa_plan(
     const std::vector<double>& scale, const std::vector<double>& bias,
     int64_t N, int64_t ws_cap_bytes) {
   const int64_t C = int64_t(scale.size());
-  for (int64_t c = 0; c < C; ++c) {
-    p.scale[c] = float(scale[c]);
-    p.bias[c] = float(bias[c]);
-  }
+  fill_scale_bias(p, scale, bias);
   p.rh = float(rh);
   p.rw = float(rw);
-  p.sup_h = p.rh >= 1.f ? p.rh : 1.f;
-  p.sup_w = p.rw >= 1.f ? p.rw : 1.f;
-  p.inv_h = p.rh >= 1.f ? float(1.0 / double(p.rh)) : 1.f;
-  p.inv_w = p.rw >= 1.f ? float(1.0 / double(p.rw)) : 1.f;
+  aa_support(p.rh, p.sup_h, p.inv_h);
+  aa_support(p.rw, p.sup_w, p.inv_w);
   p.Hin = int(Hin); p.Win = int(Win);
   p.Hc = int(Hc); p.Wc = int(Wc);
   p.top = int(top); p.left = int(left);
-  // source rows of the crop window: [lo(first row), lo(last) + size(last))
-  float unused_c;
-  int lo_first, lo_last, size_first, size_last;
-  aa_span(p.top, p.rh, p.sup_h, p.Hin, unused_c, lo_first, size_first);
-  aa_span(p.top + p.Hc - 1, p.rh, p.sup_h, p.Hin, unused_c, lo_last,
-          size_last);
-  p.y_base = lo_first;
-  p.Rs = lo_last + size_last - lo_first;
-  TORCH_CHECK(p.Rs >= 1 && p.y_base + p.Rs <= p.Hin, who,
-              ": internal row range error");
+  aa_row_range(p.top, p.Hc, p.rh, p.sup_h, p.Hin, p.y_base, p.Rs, who);
 
   const int64_t cap = ws_cap_bytes > 0 ? ws_cap_bytes : kResizeAAWsBytes;
   const int64_t img_floats = int64_t(p.Rs) * Wc * C;
@@ -2670,16 +2586,10 @@ at::Tensor u8_nhwc_resize_aa_normalize(
   TORCH_CHECK(rh > 0.0 && rw > 0.0 && rh <= double(kMaxSide) &&
               rw <= double(kMaxSide),
               "u8_nhwc_resize_aa_normalize: ratios must be in (0, 16384]");
-  TORCH_CHECK(int64_t(scale.size()) == C && int64_t(bias.size()) == C,
-              "u8_nhwc_resize_aa_normalize: scale/bias need one value per "
-              "channel");
-  TORCH_CHECK(out_dtype == at::kFloat || out_dtype == at::kBFloat16 ||
-              out_dtype == at::kHalf,
-              "u8_nhwc_resize_aa_normalize: out_dtype must be f32, bf16 or "
-              "f16");
-  auto out = out_nchw
-      ? at::empty({N, C, Hc, Wc}, in.options().dtype(out_dtype))
-      : at::empty({N, Hc, Wc, C}, in.options().dtype(out_dtype));
+  check_scale_bias("u8_nhwc_resize_aa_normalize", scale, bias, C,
+                   "one value per channel");
+  check_out_dtype("u8_nhwc_resize_aa_normalize", out_dtype);
+  auto out = image_out(in, N, C, Hc, Wc, out_dtype, out_nchw);
   if (N == 0) return out;  // zero grid: never launch
 
   U8ResizeAAParams p{};
@@ -2691,41 +2601,30 @@ at::Tensor u8_nhwc_resize_aa_normalize(
   const int64_t runs = (Wc + kResizePx - 1) / kResizePx;
   const int64_t in_img = Hin * Win * C, out_img = C * Hc * Wc;
   const auto* src = static_cast<const uint8_t*>(in.const_data_ptr());
+  const U8RaggedAAEntry* const no_table = nullptr;
 
-  auto launch = [&](auto cvt_tag, auto c_tag, auto nchw_tag) {
+  dispatch_image_out(out_dtype, C, out_nchw,
+                     [&](auto cvt_tag, auto c_tag, auto nchw_tag) {
     using CVT = decltype(cvt_tag);
     constexpr int CC = decltype(c_tag)::value;
     auto* dst = reinterpret_cast<typename CVT::Out*>(out.mutable_data_ptr());
     for (int64_t n0 = 0; n0 < N; n0 += chunk) {
       const int64_t n = std::min(chunk, N - n0);
       hipLaunchKernelGGL(
-          (u8_resize_aa_h_kernel<CC>),
+          (u8_resize_aa_h_kernel<CC, U8DenseAASrc>),
           dim3(grid_for(n * p.Rs * Wc, kResizeAABlock)), dim3(kResizeAABlock),
-          0, current_stream(), src + n0 * in_img, ws.data_ptr<float>(), n, p);
+          0, current_stream(), src + n0 * in_img, ws.data_ptr<float>(),
+          no_table, 0, n * p.Rs, p);
       HIP_CHECK(hipGetLastError());
       hipLaunchKernelGGL(
-          (u8_resize_aa_v_kernel<CVT, CC, decltype(nchw_tag)::value>),
+          (u8_resize_aa_v_kernel<CVT, CC, decltype(nchw_tag)::value,
+                                 U8DenseAASrc>),
           dim3(grid_for(n * Hc * runs, kResizeAABlock)), dim3(kResizeAABlock),
-          0, current_stream(), ws.data_ptr<float>(), dst + n0 * out_img, n,
-          p);
+          0, current_stream(), ws.data_ptr<float>(), dst + n0 * out_img,
+          no_table, n, p);
       HIP_CHECK(hipGetLastError());
     }
-  };
-  auto by_layout = [&](auto cvt_tag, auto c_tag) {
-    if (out_nchw) launch(cvt_tag, c_tag, std::true_type{});
-    else launch(cvt_tag, c_tag, std::false_type{});
-  };
-  auto by_channels = [&](auto cvt_tag) {
-    switch (C) {
-      case 1: by_layout(cvt_tag, std::integral_constant<int, 1>{}); break;
-      case 2: by_layout(cvt_tag, std::integral_constant<int, 2>{}); break;
-      case 3: by_layout(cvt_tag, std::integral_constant<int, 3>{}); break;
-      default: by_layout(cvt_tag, std::integral_constant<int, 4>{});
-    }
-  };
-  if (out_dtype == at::kFloat) by_channels(IdF32{});
-  else if (out_dtype == at::kBFloat16) by_channels(F32ToBf16{});
-  else by_channels(F32ToF16{});
+  });
   return out;
 }
 
@@ -2780,20 +2679,14 @@ at::Tensor yuv420_resize_aa_normalize(
   TORCH_CHECK(rh > 0.0 && rw > 0.0 && rh <= double(kMaxSide) &&
               rw <= double(kMaxSide),
               "yuv420_resize_aa_normalize: ratios must be in (0, 16384]");
-  TORCH_CHECK(int64_t(scale.size()) == C && int64_t(bias.size()) == C,
-              "yuv420_resize_aa_normalize: scale/bias need 3 values");
+  check_scale_bias("yuv420_resize_aa_normalize", scale, bias, C, "3 values");
   TORCH_CHECK(coef.size() == 6,
               "yuv420_resize_aa_normalize: coef needs 6 values");
   for (int64_t v : coef)   // sums stay far inside int32
     TORCH_CHECK(v >= -4096 && v <= 4096,
                 "yuv420_resize_aa_normalize: coefficient out of range");
-  TORCH_CHECK(out_dtype == at::kFloat || out_dtype == at::kBFloat16 ||
-              out_dtype == at::kHalf,
-              "yuv420_resize_aa_normalize: out_dtype must be f32, bf16 or "
-              "f16");
-  auto out = out_nchw
-      ? at::empty({N, C, Hc, Wc}, in.options().dtype(out_dtype))
-      : at::empty({N, Hc, Wc, C}, in.options().dtype(out_dtype));
+  check_out_dtype("yuv420_resize_aa_normalize", out_dtype);
+  auto out = image_out(in, N, C, Hc, Wc, out_dtype, out_nchw);
   if (N == 0) return out;  // zero grid: never launch
 
   Yuv420ResizeAAParams pp{};
@@ -2833,8 +2726,11 @@ at::Tensor yuv420_resize_aa_normalize(
   const int64_t runs = (Wc + kResizePx - 1) / kResizePx;
   const int64_t in_img = Hin * Win * 3 / 2, out_img = C * Hc * Wc;
   const auto* src = static_cast<const uint8_t*>(in.const_data_ptr());
+  const U8RaggedAAEntry* const no_table = nullptr;
 
-  auto launch = [&](auto cvt_tag, auto nchw_tag) {
+  // C is 3: the channel tag is not used
+  dispatch_image_out(out_dtype, C, out_nchw,
+                     [&](auto cvt_tag, auto, auto nchw_tag) {
     using CVT = decltype(cvt_tag);
     auto* dst = reinterpret_cast<typename CVT::Out*>(out.mutable_data_ptr());
     for (int64_t n0 = 0; n0 < N; n0 += chunk) {
@@ -2853,34 +2749,28 @@ at::Tensor yuv420_resize_aa_normalize(
             ws.data_ptr<float>(), n, pp);
       HIP_CHECK(hipGetLastError());
       hipLaunchKernelGGL(
-          (u8_resize_aa_v_kernel<CVT, 3, decltype(nchw_tag)::value>),
+          (u8_resize_aa_v_kernel<CVT, 3, decltype(nchw_tag)::value,
+                                 U8DenseAASrc>),
           dim3(grid_for(n * Hc * runs, kResizeAABlock)), dim3(kResizeAABlock),
-          0, current_stream(), ws.data_ptr<float>(), dst + n0 * out_img, n,
-          p);
+          0, current_stream(), ws.data_ptr<float>(), dst + n0 * out_img,
+          no_table, n, p);
       HIP_CHECK(hipGetLastError());
     }
-  };
-  auto by_layout = [&](auto cvt_tag) {
-    if (out_nchw) launch(cvt_tag, std::true_type{});
-    else launch(cvt_tag, std::false_type{});
-  };
-  if (out_dtype == at::kFloat) by_layout(IdF32{});
-  else if (out_dtype == at::kBFloat16) by_layout(F32ToBf16{});
-  else by_layout(F32ToF16{});
+  });
   return out;
 }
 
 // Host-side plan of an antialiased ragged batch: the device table and the
 // chunks. `table` is the int32 [N,8] rows of the bilinear ragged op
-// (U8RaggedEntry) on the HOST. For every image the row range (y_base, Rs:
-// the aa_span calls of u8_nhwc_resize_aa_normalize), its support and
-// 1/support are worked out here with the dense entry's expressions, so the
-// result is bit-identical to the dense entry on each image alone. The batch
-// is split greedily into chunks of consecutive whole images whose workspace
-// bytes, sum Rs_i*Wc*C*4, fit the cap (kResizeAAWsBytes, or `ws_cap_bytes`
-// when > 0; a chunk always holds at least one image); ws_row0 restarts at 0
-// in each chunk. Every image is checked against `in_bytes`, so a bad table
-// is an error, never an out-of-bounds read.
+// (U8RaggedEntry) on the HOST. For every image the row range (y_base, Rs),
+// its support and 1/support come from aa_row_range and aa_support, as in
+// resize_aa_plan, so the result is bit-identical to the dense entry on each
+// image alone. The batch is split greedily into chunks of consecutive whole
+// images whose workspace bytes, sum Rs_i*Wc*C*4, fit the cap
+// (kResizeAAWsBytes, or `ws_cap_bytes` when > 0; a chunk always holds at
+// least one image); ws_row0 restarts at 0 in each chunk. Every image is
+// checked against `in_bytes`, so a bad table is an error, never an
+// out-of-bounds read.
 struct RaggedAAChunk { int64_t n0, n, rows; };   // first image, count, rows
 struct RaggedAAPlan {
   at::Tensor entries;                  // int32 [N,16]: U8RaggedAAEntry rows
@@ -2936,21 +2826,10 @@ static RaggedAAPlan ragged_aa_plan(const at::Tensor& table, int64_t in_bytes,
                 e.rw <= float(kMaxSide),
                 "u8_ragged_resize_aa_normalize: image ", i,
                 ": ratios must be in (0, 16384]");
-    e.sup_h = e.rh >= 1.f ? e.rh : 1.f;
-    e.sup_w = e.rw >= 1.f ? e.rw : 1.f;
-    e.inv_h = e.rh >= 1.f ? float(1.0 / double(e.rh)) : 1.f;
-    e.inv_w = e.rw >= 1.f ? float(1.0 / double(e.rw)) : 1.f;
-    // source rows of the crop window: [lo(first row), lo(last) + size(last))
-    float unused_c;
-    int lo_first, lo_last, size_first, size_last;
-    aa_span(e.top, e.rh, e.sup_h, e.Hin, unused_c, lo_first, size_first);
-    aa_span(e.top + int(Hc) - 1, e.rh, e.sup_h, e.Hin, unused_c, lo_last,
-            size_last);
-    e.y_base = lo_first;
-    e.Rs = lo_last + size_last - lo_first;
-    TORCH_CHECK(e.Rs >= 1 && e.y_base + e.Rs <= e.Hin,
-                "u8_ragged_resize_aa_normalize: image ", i,
-                ": internal row range error");
+    aa_support(e.rh, e.sup_h, e.inv_h);
+    aa_support(e.rw, e.sup_w, e.inv_w);
+    aa_row_range(e.top, int(Hc), e.rh, e.sup_h, e.Hin, e.y_base, e.Rs,
+                 "u8_ragged_resize_aa_normalize: image ", i);
     if (chunks.empty() || (chunks.back().rows + e.Rs) * row_bytes > cap)
       chunks.push_back({i, 0, 0});
     RaggedAAChunk& ch = chunks.back();
@@ -3011,24 +2890,15 @@ at::Tensor u8_ragged_resize_aa_normalize(
               "device tensor");
   RaggedAAPlan plan =
       ragged_aa_plan(table, in.numel(), C, Hc, Wc, ws_cap_bytes, true);
-  TORCH_CHECK(int64_t(scale.size()) == C && int64_t(bias.size()) == C,
-              "u8_ragged_resize_aa_normalize: scale/bias need one value per "
-              "channel");
-  TORCH_CHECK(out_dtype == at::kFloat || out_dtype == at::kBFloat16 ||
-              out_dtype == at::kHalf,
-              "u8_ragged_resize_aa_normalize: out_dtype must be f32, bf16 or "
-              "f16");
+  check_scale_bias("u8_ragged_resize_aa_normalize", scale, bias, C,
+                   "one value per channel");
+  check_out_dtype("u8_ragged_resize_aa_normalize", out_dtype);
   const int64_t N = table.size(0);
-  auto out = out_nchw
-      ? at::empty({N, C, Hc, Wc}, in.options().dtype(out_dtype))
-      : at::empty({N, Hc, Wc, C}, in.options().dtype(out_dtype));
+  auto out = image_out(in, N, C, Hc, Wc, out_dtype, out_nchw);
   if (N == 0) return out;  // zero grid: never launch
 
   U8ResizeAAParams p{};    // the source-side fields come from the table
-  for (int64_t c = 0; c < C; ++c) {
-    p.scale[c] = float(scale[c]);
-    p.bias[c] = float(bias[c]);
-  }
+  fill_scale_bias(p, scale, bias);
   p.Hc = int(Hc); p.Wc = int(Wc);
   const auto& chunks = plan.chunks;
   int64_t max_rows = 0;
@@ -3044,40 +2914,27 @@ at::Tensor u8_ragged_resize_aa_normalize(
   const int64_t out_img = C * Hc * Wc;
   const auto* src = static_cast<const uint8_t*>(in.const_data_ptr());
 
-  auto launch = [&](auto cvt_tag, auto c_tag, auto nchw_tag) {
+  dispatch_image_out(out_dtype, C, out_nchw,
+                     [&](auto cvt_tag, auto c_tag, auto nchw_tag) {
     using CVT = decltype(cvt_tag);
     constexpr int CC = decltype(c_tag)::value;
     auto* dst = reinterpret_cast<typename CVT::Out*>(out.mutable_data_ptr());
     for (const RaggedAAChunk& ch : chunks) {
       hipLaunchKernelGGL(
-          (u8_ragged_resize_aa_h_kernel<CC>),
+          (u8_resize_aa_h_kernel<CC, U8RaggedAASrc>),
           dim3(grid_for(ch.rows * Wc, kResizeAABlock)), dim3(kResizeAABlock),
           0, current_stream(), src, ws.data_ptr<float>(), tab + ch.n0,
           int(ch.n), ch.rows, p);
       HIP_CHECK(hipGetLastError());
       hipLaunchKernelGGL(
-          (u8_ragged_resize_aa_v_kernel<CVT, CC, decltype(nchw_tag)::value>),
+          (u8_resize_aa_v_kernel<CVT, CC, decltype(nchw_tag)::value,
+                                 U8RaggedAASrc>),
           dim3(grid_for(ch.n * Hc * runs, kResizeAABlock)),
           dim3(kResizeAABlock), 0, current_stream(), ws.data_ptr<float>(),
           dst + ch.n0 * out_img, tab + ch.n0, ch.n, p);
       HIP_CHECK(hipGetLastError());
     }
-  };
-  auto by_layout = [&](auto cvt_tag, auto c_tag) {
-    if (out_nchw) launch(cvt_tag, c_tag, std::true_type{});
-    else launch(cvt_tag, c_tag, std::false_type{});
-  };
-  auto by_channels = [&](auto cvt_tag) {
-    switch (C) {
-      case 1: by_layout(cvt_tag, std::integral_constant<int, 1>{}); break;
-      case 2: by_layout(cvt_tag, std::integral_constant<int, 2>{}); break;
-      case 3: by_layout(cvt_tag, std::integral_constant<int, 3>{}); break;
-      default: by_layout(cvt_tag, std::integral_constant<int, 4>{});
-    }
-  };
-  if (out_dtype == at::kFloat) by_channels(IdF32{});
-  else if (out_dtype == at::kBFloat16) by_channels(F32ToBf16{});
-  else by_channels(F32ToF16{});
+  });
   return out;
 }
 

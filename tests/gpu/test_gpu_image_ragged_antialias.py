@@ -1,8 +1,8 @@
 """Antialiased ragged uint8 image batches on the GPU: the
-u8_ragged_resize_aa_h / _v kernels (N images of N sizes, two launches per
-chunk) against the dense antialiased op run on CPU for each image alone
-(exact equality), then end to end through the raw server and the ResNet-50
-``uint8_ragged_antialias`` mode.
+u8_resize_aa_h / _v kernels with the ragged source (N images of N sizes, two
+launches per chunk) against the dense antialiased op run on CPU for each
+image alone (exact equality), then end to end through the raw server and the
+ResNet-50 ``uint8_ragged_antialias`` mode.
 
 Paths of the two kernels and the smallest batch here that reaches each (a
 batch is a list of (Hin,Win) -> resized size / crop window, C = 3 unless
