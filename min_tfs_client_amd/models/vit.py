@@ -1,0 +1,179 @@
+"""Vision Transformer (ViT-B/16 by default) in plain PyTorch.
+
+Self-contained implementation (no checkpoint download; random init):
+pre-LayerNorm encoder blocks, a class token, learned position embeddings and
+a linear head on the class token. The embedding (``embed``) and the encoder
+(``forward_tokens``) are separate methods, so a server can replace the
+embedding by the fused uint8 patch-embedding kernel
+(``preprocess.PatchEmbedPreprocess``).
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from ..preprocess import IMAGENET_MEAN, IMAGENET_STD, PatchEmbedPreprocess
+
+
+class VitConfig:
+    image_size = 224
+    patch = 16
+    hidden = 768
+    layers = 12
+    heads = 12
+    mlp = 3072
+    num_classes = 1000
+    eps = 1e-6
+
+    def __init__(self, **overrides):
+        for key, value in overrides.items():
+            if not hasattr(type(self), key):
+                raise ValueError(f"unknown VitConfig field {key!r}")
+            setattr(self, key, value)
+
+
+class VitBlock(nn.Module):
+    def __init__(self, cfg: VitConfig):
+        super().__init__()
+        h = cfg.hidden
+        self.ln1 = nn.LayerNorm(h, eps=cfg.eps)
+        self.qkv = nn.Linear(h, 3 * h)
+        self.attn_out = nn.Linear(h, h)
+        self.ln2 = nn.LayerNorm(h, eps=cfg.eps)
+        self.ff1 = nn.Linear(h, cfg.mlp)
+        self.ff2 = nn.Linear(cfg.mlp, h)
+        self.heads = cfg.heads
+        self.head_dim = h // cfg.heads
+
+    def forward(self, x):
+        B, T, H = x.shape
+        qkv = self.qkv(self.ln1(x)).view(B, T, 3, self.heads, self.head_dim)
+        q, k, v = (t.transpose(1, 2) for t in qkv.unbind(2))
+        attn = F.scaled_dot_product_attention(q, k, v)
+        x = x + self.attn_out(attn.transpose(1, 2).reshape(B, T, H))
+        return x + self.ff2(F.gelu(self.ff1(self.ln2(x))))
+
+
+class VisionTransformer(nn.Module):
+    def __init__(self, cfg: VitConfig = None):
+        super().__init__()
+        cfg = VitConfig() if cfg is None else cfg
+        if cfg.image_size % cfg.patch or cfg.hidden % cfg.heads:
+            raise ValueError(
+                "image_size must be a multiple of patch and hidden of heads")
+        self.cfg = cfg
+        tokens = (cfg.image_size // cfg.patch) ** 2 + 1
+        self.patch_embed = nn.Conv2d(3, cfg.hidden, cfg.patch,
+                                     stride=cfg.patch)
+        self.cls_token = nn.Parameter(torch.randn(1, 1, cfg.hidden) * 0.02)
+        self.pos_embed = nn.Parameter(
+            torch.randn(1, tokens, cfg.hidden) * 0.02)
+        self.blocks = nn.ModuleList(
+            [VitBlock(cfg) for _ in range(cfg.layers)])
+        self.ln = nn.LayerNorm(cfg.hidden, eps=cfg.eps)
+        self.head = nn.Linear(cfg.hidden, cfg.num_classes)
+
+    def embed(self, x):
+        """Normalized ``[N,3,H,W]`` -> tokens ``[N,T,D]``."""
+        x = self.patch_embed(x).flatten(2).transpose(1, 2)
+        x = torch.cat((self.cls_token.expand(x.shape[0], -1, -1), x), dim=1)
+        return x + self.pos_embed
+
+    def forward_tokens(self, tokens):
+        """Tokens ``[N,T,D]`` -> logits ``[N,num_classes]``."""
+        x = tokens
+        for blk in self.blocks:
+            x = blk(x)
+        return self.head(self.ln(x)[:, 0])
+
+    def forward(self, x):
+        return self.forward_tokens(self.embed(x))
+
+
+def vit_b16(config: VitConfig = None) -> VisionTransformer:
+    return VisionTransformer(config)
+
+
+def vit_b16_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
+                     input_format: str = "float_nchw",
+                     output_format: str = "logits", top_k: int = 5,
+                     config: VitConfig = None):
+    """ViT-B/16 Servable: input alias "images", output "logits"
+    (N,num_classes).
+
+    ``input_format="float_nchw"`` (default): "images" is DT_FLOAT
+    (N,3,224,224), already normalized by the client; the model embeds it
+    itself (``VisionTransformer.forward``).
+    ``input_format="uint8_nhwc"``: "images" is DT_UINT8 (N,224,224,3) raw
+    pixels. The server turns them into the encoder's input tokens in one
+    fused kernel (``preprocess.PatchEmbedPreprocess``,
+    ``ops.image_u8_patch_embed``): ImageNet normalization, the 16x16 patch
+    projection, the class token and the position embeddings, built from the
+    module's own parameters and refolded whenever they change
+    (``load_state_dict`` after construction included); the model runs
+    ``forward_tokens``. In this mode the patch projection uses bf16 weights
+    with fp32 accumulation whatever ``dtype`` is; the pixel operand is exact.
+
+    ``output_format="logits"`` / ``"topk"`` and ``top_k``: as for
+    ``resnet50_servable`` (``postprocess.TopKClassification``).
+    ``config`` replaces the ViT-B/16 ``VitConfig`` (image size, patch, width,
+    depth), e.g. a one-layer model in tests."""
+    from ..postprocess import TopKClassification
+    from ..server import Servable
+
+    if input_format not in ("float_nchw", "uint8_nhwc"):
+        raise ValueError(
+            f"input_format must be 'float_nchw' or 'uint8_nhwc', got "
+            f"{input_format!r}")
+    if output_format not in ("logits", "topk"):
+        raise ValueError(
+            f"output_format must be 'logits' or 'topk', got "
+            f"{output_format!r}")
+    topk = output_format == "topk"
+    # top_k is validated in every mode: a typo must not wait for "topk"
+    postprocess = TopKClassification(top_k)
+    cfg = VitConfig() if config is None else config
+    u8 = input_format == "uint8_nhwc"
+
+    torch.manual_seed(seed)
+    model = vit_b16(cfg).to(device=device, dtype=dtype).eval()
+
+    @torch.no_grad()
+    def fn(inputs):
+        x = inputs["images"]
+        if not isinstance(x, torch.Tensor):
+            x = torch.as_tensor(x)
+        # a no-op (same tensor) when preprocessing already produced
+        # device/dtype
+        x = x.to(device=device, dtype=dtype)
+        logits = s.module.forward_tokens(x) if u8 else s.module(x)
+        # the top-k head reads the model's own dtype
+        return {"logits": logits if topk else logits.float()}
+
+    size = cfg.image_size
+    if u8:
+        images_sig = (4, [-1, size, size, 3])               # DT_UINT8
+        preprocess = {"images": PatchEmbedPreprocess(
+            model.patch_embed.weight, model.patch_embed.bias, IMAGENET_MEAN,
+            IMAGENET_STD, pos_embed=model.pos_embed,
+            cls_token=model.cls_token, out_dtype=dtype, device=device)}
+    else:
+        images_sig = (1, [-1, 3, size, size])               # DT_FLOAT
+        preprocess = None
+    if topk:
+        outputs = {"scores": (1, [-1, postprocess.k]),      # DT_FLOAT
+                   "classes": (3, [-1, postprocess.k])}     # DT_INT32
+    else:
+        outputs = {"logits": (1, [-1, cfg.num_classes])}
+    s = Servable(
+        fn,
+        signature={
+            "method_name": "tensorflow/serving/predict",
+            "inputs": {"images": images_sig},
+            "outputs": outputs,
+        },
+        preprocess=preprocess,
+        postprocess=postprocess if topk else None)
+    s.module = model
+    return s

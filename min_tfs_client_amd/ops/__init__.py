@@ -765,6 +765,170 @@ def image_u8_ragged_resize_to_float(data, shapes, sizes, out_size, mean, std,
     return torch.cat(outs)
 
 
+PATCH_EMBED_PATCHES = (14, 16, 32)
+
+
+def patch_embed_fold(weight, bias, mean, std, pixel_scale=1.0 / 255.0):
+    """Fold the per-channel normalization into a ViT patch projection, once
+    per model, on the host: ``(wk, bias_f)`` for :func:`image_u8_patch_embed`.
+
+    ``weight`` is the conv weight ``[D,3,P,P]``, ``bias`` its ``[D]`` bias or
+    ``None``. With ``(scale, bias_c) = normalization_constants(mean, std,
+    pixel_scale)``, so that the normalized pixel is ``u8 * scale_c +
+    bias_c``::
+
+        wk[d, (py*P + px)*3 + c] = bf16_rne(W[d,c,py,px] * scale_c)
+        bias_f[d] = fp32(bias[d] + sum W[d,c,py,px] * bias_c)
+
+    Products and the sum are fp64, from the unrounded ``W``; the bf16
+    rounding is one round-to-nearest-even straight from fp64 (normal range).
+    ``wk`` is bf16 ``[D,Kp]``, ``Kp`` = ``3*P*P`` rounded up to a multiple of
+    32 with a zero tail; ``bias_f`` is fp32 ``[D]``; both are on the device
+    of ``weight``. Deterministic."""
+    if not isinstance(weight, torch.Tensor) or weight.dim() != 4 or \
+            weight.shape[1] != 3 or weight.shape[2] != weight.shape[3] or \
+            not weight.is_floating_point():
+        raise ValueError(
+            "patch_embed_fold expects a float conv weight [D,3,P,P], got "
+            f"{getattr(weight, 'shape', weight)!r}")
+    D, P = int(weight.shape[0]), int(weight.shape[2])
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError(
+            f"mean/std need 3 entries (R, G, B), got {len(mean)}/{len(std)}")
+    if bias is not None and tuple(bias.shape) != (D,):
+        raise ValueError(
+            f"bias must have shape {[D]}, got {list(bias.shape)}")
+    scale, bias_c = normalization_constants(mean, std, pixel_scale)
+    w = weight.detach().cpu().double()
+    s = torch.tensor(scale, dtype=torch.float64).view(1, 3, 1, 1)
+    b = torch.tensor(bias_c, dtype=torch.float64).view(1, 3, 1, 1)
+    K = 3 * P * P
+    # 8 significant bits, ties to even; .to(bfloat16) is then exact (a cast
+    # of the fp64 product would round twice, through fp32)
+    mant, exp = torch.frexp((w * s).permute(0, 2, 3, 1).reshape(D, K))
+    wk = torch.zeros((D, (K + 31) // 32 * 32), dtype=torch.bfloat16)
+    wk[:, :K] = torch.ldexp(torch.round(mant * 256.0), exp - 8).to(
+        torch.bfloat16)
+    bias_f = (w * b).sum((1, 2, 3))
+    if bias is not None:
+        bias_f = bias_f + bias.detach().cpu().double()
+    return wk.to(weight.device), bias_f.float().to(weight.device)
+
+
+def image_u8_patch_embed(images, wk, bias_f, patch, pos_embed=None,
+                         cls_token=None, out_dtype=None):
+    """Fused ViT patch embedding of raw pixels: contiguous uint8
+    ``[N,H,W,3]`` images -> tokens ``[N,T,D]``, normalization, patch
+    projection, class token and position embedding in one kernel launch.
+
+    ``(wk, bias_f)`` come from :func:`patch_embed_fold`: bf16 ``[D,Kp]`` and
+    fp32 ``[D]``, ``D`` a multiple of 16. ``patch`` is 14, 16 or 32 and
+    divides ``H`` and ``W``; ``Hp = H/patch``, ``Wp = W/patch``. ``cls_token``
+    is fp32 ``[D]`` or ``None``, ``pos_embed`` fp32 ``[T,D]`` or ``None``,
+    with ``T = Hp*Wp + (1 if cls_token is given else 0)``::
+
+        out[n, t0 + hp*Wp + wp, d] = out_dtype(
+            sum_k u8(n, hp*P+py, wp*P+px, c) * wk[d, (py*P+px)*3+c]
+            + bias_f[d] + pos_embed[t0 + hp*Wp + wp, d])
+        out[n, 0, d] = out_dtype(cls_token[d] + pos_embed[0, d])   # t0 = 1
+
+    The pixel operand is exact (every byte is a bf16 number); the products
+    run on the bf16 matrix cores with fp32 accumulation, the rest is fp32
+    and one round-to-nearest-even conversion to ``out_dtype`` (float32, the
+    default, bfloat16 or float16). The only approximation against an fp32
+    model on normalized input is the bf16 rounding of the folded weights.
+    Deterministic: the same input gives bit-identical output on every run.
+
+    Device tensors run the gfx950 kernel (no eager fallback); CPU tensors
+    use an eager fp32 expression with the same semantics, so CPU-only servers
+    work too. ``N == 0`` returns an empty tensor. Invalid arguments raise
+    ``ValueError`` on both paths. The kernel loads pixels 16 bytes at a time:
+    a device ``images`` whose storage is not 16-byte aligned (a view at an
+    odd offset; fresh tensors are aligned) is copied once before the
+    launch."""
+    return _image_u8_patch_embed(images, wk, bias_f, patch, pos_embed,
+                                 cls_token, out_dtype, 0)
+
+
+def _image_u8_patch_embed(images, wk, bias_f, patch, pos_embed, cls_token,
+                          out_dtype, tile):
+    """:func:`image_u8_patch_embed` with the kernel's tile forced, for tests
+    and the bench tool: ``tile`` 0 is the kernel's own rule, 1 the small
+    tile, 2 the large one. The CPU path has no tiles."""
+    name = "image_u8_patch_embed"
+    if out_dtype is None:
+        out_dtype = torch.float32
+    if out_dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError(
+            f"out_dtype must be float32, bfloat16 or float16, got {out_dtype}")
+    if isinstance(patch, bool) or patch not in PATCH_EMBED_PATCHES:
+        raise ValueError(
+            f"patch must be one of {PATCH_EMBED_PATCHES}, got {patch!r}")
+    P = int(patch)
+    if not isinstance(images, torch.Tensor):
+        raise ValueError(f"{name} expects a torch tensor")
+    if images.dtype != torch.uint8:
+        raise ValueError(f"{name} expects uint8 pixels, got {images.dtype}")
+    if images.dim() != 4:
+        raise ValueError(f"{name} expects [N,H,W,3], got rank {images.dim()}")
+    N, H, W, C = (int(d) for d in images.shape)
+    if C != 3:
+        raise ValueError(f"{name} expects 3 channels, got {C}")
+    if H < P or W < P or H % P or W % P:
+        raise ValueError(
+            f"{name}: H and W must be positive multiples of patch {P}, got "
+            f"{H}x{W}")
+    K = 3 * P * P
+    Kp = (K + 31) // 32 * 32
+    if not isinstance(wk, torch.Tensor) or wk.dtype != torch.bfloat16 or \
+            wk.dim() != 2 or wk.shape[1] != Kp or wk.shape[0] < 16 or \
+            wk.shape[0] % 16:
+        raise ValueError(
+            f"wk must be bfloat16 [D,{Kp}] with D a multiple of 16, got "
+            f"{getattr(wk, 'dtype', None)} {list(getattr(wk, 'shape', ()))}")
+    D = int(wk.shape[0])
+    t0 = 0 if cls_token is None else 1
+    T = (H // P) * (W // P) + t0
+    for label, t, shape in (("bias_f", bias_f, (D,)),
+                            ("pos_embed", pos_embed, (T, D)),
+                            ("cls_token", cls_token, (D,))):
+        if t is None and label != "bias_f":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or \
+                tuple(t.shape) != shape:
+            raise ValueError(
+                f"{label} must be float32 {list(shape)}, got "
+                f"{getattr(t, 'dtype', None)} "
+                f"{list(getattr(t, 'shape', ()))}")
+    for label, t in (("images", images), ("wk", wk), ("bias_f", bias_f),
+                     ("pos_embed", pos_embed), ("cls_token", cls_token)):
+        if t is None:
+            continue
+        if not t.is_contiguous():
+            raise ValueError(f"{name} expects a contiguous {label}")
+        if t.device != images.device:
+            raise ValueError(
+                f"{label} is on {t.device} but images is on {images.device}")
+    if N == 0:
+        return torch.empty((0, T, D), dtype=out_dtype, device=images.device)
+    if images.is_cuda:
+        if images.data_ptr() % 16:      # the kernel loads 16 bytes at a time
+            images = images.clone()
+        return require_native().u8_patch_embed(
+            images, wk, bias_f, P, pos_embed, cls_token, out_dtype,
+            int(tile))
+    Hp, Wp = H // P, W // P
+    a = images.view(N, Hp, P, Wp, P, 3).permute(0, 1, 3, 2, 4, 5).reshape(
+        N * Hp * Wp, K).float()
+    y = ((a @ wk[:, :K].float().t()) + bias_f).view(N, Hp * Wp, D)
+    if pos_embed is not None:
+        y = y + pos_embed[t0:]
+    if cls_token is not None:
+        row = cls_token if pos_embed is None else cls_token + pos_embed[0]
+        y = torch.cat((row.expand(N, 1, D), y), dim=1)
+    return y.to(out_dtype).contiguous()
+
+
 def masked_mean_pool(hidden, mask=None, normalize=False):
     """Fused masked mean-pool head: ``[B,S,H]`` hidden state (f32, bf16 or
     f16, contiguous) -> fp32 ``[B,H]``, one vector per sequence.

@@ -68,6 +68,12 @@ at::Tensor masked_mean_pool(const at::Tensor& hidden,
 std::tuple<at::Tensor, at::Tensor> softmax_topk(const at::Tensor& logits,
                                                 int64_t k);
 at::Tensor quantize_q8(const at::Tensor& in, double scale, double zp);
+// implemented in patch_embed.hip
+at::Tensor u8_patch_embed(const at::Tensor& images, const at::Tensor& wk,
+                          const at::Tensor& bias, int64_t patch,
+                          const c10::optional<at::Tensor>& pos,
+                          const c10::optional<at::Tensor>& cls,
+                          at::ScalarType out_dtype, int64_t tile);
 at::Tensor dequantize_q8(const at::Tensor& in, double scale, double zp);
 void copy_device_to_host_ptr(const at::Tensor& src, void* dst, size_t n,
                              int mode);
@@ -702,6 +708,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("mask") = py::none(), py::arg("normalize") = false);
   m.def("softmax_topk", &mi355x::softmax_topk, py::arg("logits"),
         py::arg("k"));
+  m.def("u8_patch_embed", &mi355x::u8_patch_embed, py::arg("images"),
+        py::arg("wk"), py::arg("bias"), py::arg("patch"),
+        py::arg("pos"), py::arg("cls"),
+        py::arg("out_dtype"), py::arg("tile") = 0);
   m.def("quantize_q8", &mi355x::quantize_q8, py::arg("input"),
         py::arg("scale"), py::arg("zero_point") = 0.0);
   m.def("dequantize_q8", &mi355x::dequantize_q8, py::arg("input"),

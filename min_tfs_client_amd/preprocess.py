@@ -20,9 +20,13 @@ images of N different sizes packed back to back (``pack_ragged_images``) and
 one kernel launch (``ops.image_u8_ragged_resize_to_float``) turns them into
 one batch; ``AntialiasedRaggedImagePreprocess`` does the same with the
 antialiased filter, in two launches.
+``PatchEmbedPreprocess`` is the Vision Transformer case: uint8 pixels go
+straight to encoder tokens, normalization, patch projection, class token and
+position embedding in one matrix-core kernel (``ops.image_u8_patch_embed``).
 """
 from __future__ import annotations
 
+import threading
 import warnings
 
 import numpy as np
@@ -341,6 +345,79 @@ class AntialiasedRaggedImagePreprocess(RaggedImagePreprocess):
         super().__init__(mean, std, out_dtype=out_dtype, layout=layout,
                          pixel_scale=pixel_scale, device=device,
                          resize=resize, center_crop=center_crop)
+
+
+class PatchEmbedPreprocess:
+    """uint8 ``[N,H,W,3]`` pixels -> ViT tokens ``[N,T,D]``: normalization,
+    patch projection, class token and position embedding in one kernel
+    (``ops.image_u8_patch_embed``).
+
+    ``weight`` ``[D,3,P,P]`` and ``bias`` are the patch convolution's
+    parameters, ``pos_embed`` (``T*D`` values) and ``cls_token`` (``D``
+    values) the model's, any float dtype; ``None`` leaves a term out. The
+    hook keeps references to them and folds lazily (``ops.patch_embed_fold``;
+    position and class embeddings as fp32): on the first call, and again
+    whenever one of them has changed since the last fold. In-place updates
+    such as ``load_state_dict`` bump ``tensor._version``, so a servable that
+    loads its weights after construction serves the loaded ones.
+
+    Accepts a numpy array or a torch tensor, on CPU or device. With
+    ``device`` set, the **uint8** bytes are moved there first and the folded
+    operands live there. The projection uses bf16 weights with fp32
+    accumulation whatever ``out_dtype`` is. Invalid input raises
+    ``ValueError`` (servers answer INVALID_ARGUMENT)."""
+
+    def __init__(self, weight, bias, mean, std, pos_embed=None,
+                 cls_token=None, out_dtype=None,
+                 pixel_scale: float = 1.0 / 255.0, device=None):
+        self.weight, self.bias = weight, bias
+        self.pos_embed, self.cls_token = pos_embed, cls_token
+        self.mean = tuple(float(m) for m in mean)
+        self.std = tuple(float(s) for s in std)
+        self.out_dtype = torch.float32 if out_dtype is None else out_dtype
+        self.pixel_scale = pixel_scale
+        self.device = device
+        self.patch = int(weight.shape[-1])
+        self._lock = threading.Lock()
+        self._key = None
+        self._folded = None
+        # fail at construction, not on the first request
+        ops.normalization_constants(self.mean, self.std, pixel_scale)
+
+    def _sources(self):
+        return (self.weight, self.bias, self.pos_embed, self.cls_token)
+
+    def folded(self):
+        """``(wk, bias_f, pos, cls)`` for the parameters as they are now."""
+        key = tuple(None if t is None else (t._version, t.data_ptr(), t.device)
+                    for t in self._sources())
+        with self._lock:
+            if key != self._key:
+                wk, bias_f = ops.patch_embed_fold(
+                    self.weight, self.bias, self.mean, self.std,
+                    self.pixel_scale)
+                dev = self.weight.device if self.device is None \
+                    else self.device
+                D = wk.shape[0]
+                pos = cls = None
+                if self.pos_embed is not None:
+                    pos = self.pos_embed.detach().float().reshape(
+                        -1, D).to(dev).contiguous()
+                if self.cls_token is not None:
+                    cls = self.cls_token.detach().float().reshape(
+                        D).to(dev).contiguous()
+                self._folded = (wk.to(dev), bias_f.to(dev), pos, cls)
+                self._key = key
+            return self._folded
+
+    def __call__(self, x):
+        x = _as_tensor(x)
+        if self.device is not None and x.dtype == torch.uint8:
+            x = x.to(self.device)
+        wk, bias_f, pos, cls = self.folded()
+        return ops.image_u8_patch_embed(
+            x, wk, bias_f, self.patch, pos_embed=pos, cls_token=cls,
+            out_dtype=self.out_dtype)
 
 
 def pack_ragged_images(images):

@@ -13,7 +13,7 @@ before a version goes AVAILABLE (saved_model_warmup.cc:55-83).
 
 On-disk version-directory formats understood by the default loader:
   * ``identity``            — empty marker file -> identity echo servable
-  * ``model.json``          — {"family": "resnet50"|"bert_base",
+  * ``model.json``          — {"family": "resnet50"|"bert_base"|"vit_b16",
                                "device": ..., "state_dict": "weights.pt"?}
                                plus optional I/O modes: "input_format"
                                (resnet50: "float_nchw", "uint8_nhwc",
@@ -32,7 +32,11 @@ On-disk version-directory formats understood by the default loader:
                                "topk"; bert_base: "hidden" or
                                "sentence_embedding"), "top_k" (resnet50,
                                with "topk": 1..64 classes per image) and
-                               "normalize_embedding" (bert_base)
+                               "normalize_embedding" (bert_base); vit_b16
+                               takes "input_format" ("float_nchw" or
+                               "uint8_nhwc": raw pixels into the fused
+                               patch-embedding kernel), "output_format"
+                               ("logits" or "topk") and "top_k"
   * ``model.pt``            — TorchScript module (torch.jit.load)
 plus TF-style ``assets.extra/tf_serving_warmup_requests`` (a TFRecord of
 serialized PredictionLog protos — framing per TF's RecordWriter: length,
@@ -192,6 +196,12 @@ def default_loader(name: str, version_dir: str,
                      for k in ("output_format", "normalize_embedding")
                      if k in cfg}
             servable = bert_servable(device, **modes)
+        elif family == "vit_b16":
+            from .models import vit_b16_servable
+            modes = {k: cfg[k]
+                     for k in ("input_format", "output_format", "top_k")
+                     if k in cfg}
+            servable = vit_b16_servable(device, **modes)
         elif family == "identity":
             servable = identity_servable()
         else:

@@ -26,6 +26,7 @@ ext = CUDAExtension(
     sources=[
         os.path.join(_CSRC, "native.cpp"),
         os.path.join(_CSRC, "pack_kernels.hip"),
+        os.path.join(_CSRC, "patch_embed.hip"),
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],

@@ -1,0 +1,124 @@
+#!/usr/bin/env python3
+"""ViT patch embedding from uint8 pixels: the fused MFMA kernel against the
+composed chain a user would run without it, one GPU.
+
+    python tools/bench_patch_embed.py          # JSON lines
+
+The parent process never touches the GPU; the timings run in one fresh child
+process under a time limit, and the tool exits non-zero if it fails.
+
+Fused: ``ops.image_u8_patch_embed`` (one launch). Baseline, four passes:
+
+    ImagePreprocess (u8 NHWC -> normalized NCHW, model dtype)
+    -> F.conv2d(P x P, stride P) -> flatten/transpose
+    -> cat class token -> + pos_embed
+
+ViT-B/16 shapes: 224x224, D = 768, batch 1, 8, 32 and 128, model dtype bf16
+and fp32 (the fused projection is bf16 x bf16 -> fp32 in both; the baseline
+convolves in the model dtype). Interleaved rounds in one process, the median
+round is reported. ``fused_GB_s`` counts the bytes the fused op must move:
+pixels in, tokens out, weights once (15.7 MB for 32 images in bf16, 1.2 MB
+of it weights).
+``max_abs_diff`` against the baseline is reported, not asserted: the
+baseline rounds the normalized pixel and the weights differently.
+"""
+import json
+import os
+import subprocess
+import sys
+
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, _ROOT)
+
+BATCHES = (1, 8, 32, 128)
+DTYPES = ("bfloat16", "float32")
+TILES = {"rule": 0, "small": 1, "large": 2}
+TIMEOUT_S = 300
+
+
+def time_kernel(fn, reps, warmup):
+    import torch
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    start = torch.cuda.Event(enable_timing=True)
+    end = torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(reps):
+        fn()
+    end.record()
+    torch.cuda.synchronize()
+    return start.elapsed_time(end) / reps  # ms
+
+
+def run_cases():
+    import torch
+    import torch.nn.functional as F
+
+    from min_tfs_client_amd import ops
+    from min_tfs_client_amd.preprocess import (IMAGENET_MEAN, IMAGENET_STD,
+                                               ImagePreprocess)
+
+    dev, P, D, S = "cuda:0", 16, 768, 224
+    T = (S // P) ** 2 + 1
+    g = torch.Generator().manual_seed(0)
+    w = torch.randn((D, 3, P, P), generator=g) * 0.02
+    b = torch.randn(D, generator=g) * 0.02
+    pos = (torch.randn((T, D), generator=g) * 0.02).to(dev)
+    cls = (torch.randn(D, generator=g) * 0.02).to(dev)
+    wk, bias_f = (t.to(dev) for t in ops.patch_embed_fold(
+        w, b, IMAGENET_MEAN, IMAGENET_STD))
+    for dtype_name in DTYPES:
+        dtype = getattr(torch, dtype_name)
+        pre = ImagePreprocess(IMAGENET_MEAN, IMAGENET_STD, out_dtype=dtype)
+        w_m, b_m = w.to(dev, dtype), b.to(dev, dtype)
+        pos_m, cls_m = pos.to(dtype).view(1, T, D), cls.to(dtype).view(1, 1, D)
+        for N in BATCHES:
+            x = torch.randint(0, 256, (N, S, S, 3), dtype=torch.uint8,
+                              generator=g).to(dev)
+
+            def fused(tile=0):
+                return ops._image_u8_patch_embed(
+                    x, wk, bias_f, P, pos, cls, dtype, tile)
+
+            def baseline():
+                y = F.conv2d(pre(x), w_m, b_m, stride=P)
+                y = y.flatten(2).transpose(1, 2)
+                return torch.cat((cls_m.expand(N, -1, -1), y), 1) + pos_m
+
+            diff = (fused().float() - baseline().float()).abs().max().item()
+            reps = 200 if N <= 32 else 50
+            fns = [lambda t=t: fused(t) for t in TILES.values()] + [baseline]
+            rounds = [[time_kernel(f, reps, 10) for f in fns]
+                      for _ in range(5)]
+            ms = [sorted(r[i] for r in rounds)[2] for i in range(len(fns))]
+            nbytes = x.numel() + N * T * D * x.new_empty(
+                0, dtype=dtype).element_size() + wk.numel() * 2
+            row = {"case": f"{N}x{S}x{S}_{dtype_name}", "bytes": nbytes}
+            for name, t in zip(TILES, ms):
+                row[f"fused_{name}_ms"] = round(t, 4)
+            row.update({
+                "baseline_ms": round(ms[-1], 4),
+                "baseline_over_fused": round(ms[-1] / ms[0], 2),
+                "fused_GB_s": round(nbytes / 1e9 / (ms[0] / 1e3), 1),
+                "max_abs_diff": diff})
+            print(json.dumps(row), flush=True)
+
+
+def main():
+    if sys.argv[1:] == ["--cases"]:
+        return run_cases()
+    cmd = [sys.executable, os.path.abspath(__file__), "--cases"]
+    try:
+        rc = subprocess.run(cmd, timeout=TIMEOUT_S).returncode
+    except subprocess.TimeoutExpired:
+        print(json.dumps({"error": "timeout", "timeout_s": TIMEOUT_S}),
+              flush=True)
+        sys.exit(124)
+    if rc != 0:
+        print(json.dumps({"error": "failed", "exit": rc}), flush=True)
+        sys.exit(rc if rc > 0 else 1)
+
+
+if __name__ == "__main__":
+    main()
