@@ -13,7 +13,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..preprocess import IMAGENET_MEAN, IMAGENET_STD, PatchEmbedPreprocess
+from ..preprocess import (IMAGENET_MEAN, IMAGENET_STD, PatchEmbedPreprocess,
+                          Yuv420PatchEmbedPreprocess)
 
 
 class VitConfig:
@@ -98,7 +99,7 @@ def vit_b16(config: VitConfig = None) -> VisionTransformer:
 def vit_b16_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
                      input_format: str = "float_nchw",
                      output_format: str = "logits", top_k: int = 5,
-                     config: VitConfig = None):
+                     config: VitConfig = None, yuv_matrix: str = "bt601"):
     """ViT-B/16 Servable: input alias "images", output "logits"
     (N,num_classes).
 
@@ -114,6 +115,15 @@ def vit_b16_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
     (``load_state_dict`` after construction included); the model runs
     ``forward_tokens``. In this mode the patch projection uses bf16 weights
     with fp32 accumulation whatever ``dtype`` is; the pixel operand is exact.
+    ``input_format="nv12"`` / ``"i420"``: "images" is DT_UINT8
+    (N,224*3/2,224), YUV 4:2:0 frames as a video or JPEG decoder emits them
+    (layout: ``ops.yuv420_to_rgb_u8``), half the request bytes of
+    ``uint8_nhwc``. The same kernel converts them to RGB with the integer
+    matrix ``yuv_matrix`` ("bt601", the default, "bt709" or "bt601_full")
+    while it fills its tile (``preprocess.Yuv420PatchEmbedPreprocess``,
+    ``ops.image_yuv420_patch_embed``): the logits are exactly those of
+    ``uint8_nhwc`` on the converted frames. The patch must be 16 or 32. A
+    non-default ``yuv_matrix`` is rejected in every other mode.
 
     ``output_format="logits"`` / ``"topk"`` and ``top_k``: as for
     ``resnet50_servable`` (``postprocess.TopKClassification``).
@@ -122,9 +132,14 @@ def vit_b16_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
     from ..postprocess import TopKClassification
     from ..server import Servable
 
-    if input_format not in ("float_nchw", "uint8_nhwc"):
+    if input_format not in ("float_nchw", "uint8_nhwc", "nv12", "i420"):
         raise ValueError(
-            f"input_format must be 'float_nchw' or 'uint8_nhwc', got "
+            f"input_format must be 'float_nchw', 'uint8_nhwc', 'nv12' or "
+            f"'i420', got {input_format!r}")
+    yuv = input_format in ("nv12", "i420")
+    if yuv_matrix != "bt601" and not yuv:
+        raise ValueError(
+            "yuv_matrix needs a YUV input_format ('nv12' or 'i420'), got "
             f"{input_format!r}")
     if output_format not in ("logits", "topk"):
         raise ValueError(
@@ -134,7 +149,7 @@ def vit_b16_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
     # top_k is validated in every mode: a typo must not wait for "topk"
     postprocess = TopKClassification(top_k)
     cfg = VitConfig() if config is None else config
-    u8 = input_format == "uint8_nhwc"
+    u8 = input_format == "uint8_nhwc" or yuv      # tokens from the kernel
 
     torch.manual_seed(seed)
     model = vit_b16(cfg).to(device=device, dtype=dtype).eval()
@@ -152,7 +167,14 @@ def vit_b16_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
         return {"logits": logits if topk else logits.float()}
 
     size = cfg.image_size
-    if u8:
+    if yuv:
+        images_sig = (4, [-1, size * 3 // 2, size])         # DT_UINT8
+        preprocess = {"images": Yuv420PatchEmbedPreprocess(
+            model.patch_embed.weight, model.patch_embed.bias, IMAGENET_MEAN,
+            IMAGENET_STD, pos_embed=model.pos_embed,
+            cls_token=model.cls_token, out_dtype=dtype, device=device,
+            chroma=input_format, matrix=yuv_matrix)}
+    elif u8:
         images_sig = (4, [-1, size, size, 3])               # DT_UINT8
         preprocess = {"images": PatchEmbedPreprocess(
             model.patch_embed.weight, model.patch_embed.bias, IMAGENET_MEAN,

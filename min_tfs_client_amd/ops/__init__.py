@@ -856,11 +856,7 @@ def _image_u8_patch_embed(images, wk, bias_f, patch, pos_embed, cls_token,
     and the bench tool: ``tile`` 0 is the kernel's own rule, 1 the small
     tile, 2 the large one. The CPU path has no tiles."""
     name = "image_u8_patch_embed"
-    if out_dtype is None:
-        out_dtype = torch.float32
-    if out_dtype not in (torch.float32, torch.bfloat16, torch.float16):
-        raise ValueError(
-            f"out_dtype must be float32, bfloat16 or float16, got {out_dtype}")
+    out_dtype = _patch_embed_out_dtype(out_dtype)
     if isinstance(patch, bool) or patch not in PATCH_EMBED_PATCHES:
         raise ValueError(
             f"patch must be one of {PATCH_EMBED_PATCHES}, got {patch!r}")
@@ -874,6 +870,43 @@ def _image_u8_patch_embed(images, wk, bias_f, patch, pos_embed, cls_token,
     N, H, W, C = (int(d) for d in images.shape)
     if C != 3:
         raise ValueError(f"{name} expects 3 channels, got {C}")
+    out_dtype, T, D = _patch_embed_operands(
+        name, images, H, W, P, wk, bias_f, pos_embed, cls_token, out_dtype)
+    if N == 0:
+        return torch.empty((0, T, D), dtype=out_dtype, device=images.device)
+    if images.is_cuda:
+        if images.data_ptr() % 16:      # the kernel loads 16 bytes at a time
+            images = images.clone()
+        return require_native().u8_patch_embed(
+            images, wk, bias_f, P, pos_embed, cls_token, out_dtype,
+            int(tile))
+    K, t0 = 3 * P * P, T - (H // P) * (W // P)
+    Hp, Wp = H // P, W // P
+    a = images.view(N, Hp, P, Wp, P, 3).permute(0, 1, 3, 2, 4, 5).reshape(
+        N * Hp * Wp, K).float()
+    y = ((a @ wk[:, :K].float().t()) + bias_f).view(N, Hp * Wp, D)
+    if pos_embed is not None:
+        y = y + pos_embed[t0:]
+    if cls_token is not None:
+        row = cls_token if pos_embed is None else cls_token + pos_embed[0]
+        y = torch.cat((row.expand(N, 1, D), y), dim=1)
+    return y.to(out_dtype).contiguous()
+
+
+def _patch_embed_out_dtype(out_dtype):
+    if out_dtype is None:
+        return torch.float32
+    if out_dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError(
+            f"out_dtype must be float32, bfloat16 or float16, got {out_dtype}")
+    return out_dtype
+
+
+def _patch_embed_operands(name, images, H, W, P, wk, bias_f, pos_embed,
+                          cls_token, out_dtype):
+    """The checks the RGB and the YUV patch embedding share, for ``images``
+    of ``H x W`` pixels: ``(out_dtype, T, D)``."""
+    out_dtype = _patch_embed_out_dtype(out_dtype)
     if H < P or W < P or H % P or W % P:
         raise ValueError(
             f"{name}: H and W must be positive multiples of patch {P}, got "
@@ -909,24 +942,68 @@ def _image_u8_patch_embed(images, wk, bias_f, patch, pos_embed, cls_token,
         if t.device != images.device:
             raise ValueError(
                 f"{label} is on {t.device} but images is on {images.device}")
+    return out_dtype, T, D
+
+
+YUV420_PATCH_EMBED_PATCHES = (16, 32)
+
+
+def image_yuv420_patch_embed(frames, wk, bias_f, patch, pos_embed=None,
+                             cls_token=None, out_dtype=None, *,
+                             chroma="nv12", matrix="bt601"):
+    """Fused ViT patch embedding of YUV 4:2:0 frames: contiguous uint8
+    ``[N,H*3/2,W]`` NV12 or I420 frames (layout, ``chroma`` and ``matrix``:
+    see :func:`yuv420_to_rgb_u8`) -> tokens ``[N,T,D]`` in one kernel launch,
+    from half the bytes of RGB. The contract, bit for bit::
+
+        image_yuv420_patch_embed(x, wk, bias_f, patch, pos_embed, cls_token,
+                                 out_dtype, chroma=chroma, matrix=matrix)
+          == image_u8_patch_embed(yuv420_to_rgb_u8(x, chroma, matrix),
+                                  wk, bias_f, patch, pos_embed, cls_token,
+                                  out_dtype)
+
+    so ``(wk, bias_f)`` are those of :func:`patch_embed_fold`, unchanged, and
+    every other argument and property is that of
+    :func:`image_u8_patch_embed`: the converted pixel is a uint8 value, exact
+    in bf16. ``patch`` is 16 or 32 (14 is not served from YUV) and divides
+    ``H`` and ``W``.
+
+    Device tensors run the gfx950 kernel, which converts while it fills its
+    tile: the RGB image never exists in device memory, no eager fallback.
+    CPU tensors run exactly the two-step expression above. ``N == 0`` returns
+    an empty tensor. Invalid arguments raise ``ValueError`` on both paths. A
+    device ``frames`` whose storage is not 16-byte aligned is copied once
+    before the launch."""
+    return _image_yuv420_patch_embed(frames, wk, bias_f, patch, pos_embed,
+                                     cls_token, out_dtype, 0, chroma=chroma,
+                                     matrix=matrix)
+
+
+def _image_yuv420_patch_embed(frames, wk, bias_f, patch, pos_embed,
+                              cls_token, out_dtype, tile, *, chroma="nv12",
+                              matrix="bt601"):
+    """:func:`image_yuv420_patch_embed` with the kernel's tile forced, as
+    :func:`_image_u8_patch_embed`."""
+    name = "image_yuv420_patch_embed"
+    if isinstance(patch, bool) or patch not in YUV420_PATCH_EMBED_PATCHES:
+        raise ValueError(
+            f"{name}: patch must be one of {YUV420_PATCH_EMBED_PATCHES}, got "
+            f"{patch!r}")
+    P = int(patch)
+    N, H, W = _yuv420_frame_size(frames, chroma, matrix, name)
+    out_dtype, T, D = _patch_embed_operands(
+        name, frames, H, W, P, wk, bias_f, pos_embed, cls_token, out_dtype)
     if N == 0:
-        return torch.empty((0, T, D), dtype=out_dtype, device=images.device)
-    if images.is_cuda:
-        if images.data_ptr() % 16:      # the kernel loads 16 bytes at a time
-            images = images.clone()
-        return require_native().u8_patch_embed(
-            images, wk, bias_f, P, pos_embed, cls_token, out_dtype,
-            int(tile))
-    Hp, Wp = H // P, W // P
-    a = images.view(N, Hp, P, Wp, P, 3).permute(0, 1, 3, 2, 4, 5).reshape(
-        N * Hp * Wp, K).float()
-    y = ((a @ wk[:, :K].float().t()) + bias_f).view(N, Hp * Wp, D)
-    if pos_embed is not None:
-        y = y + pos_embed[t0:]
-    if cls_token is not None:
-        row = cls_token if pos_embed is None else cls_token + pos_embed[0]
-        y = torch.cat((row.expand(N, 1, D), y), dim=1)
-    return y.to(out_dtype).contiguous()
+        return torch.empty((0, T, D), dtype=out_dtype, device=frames.device)
+    if frames.is_cuda:
+        if frames.data_ptr() % 16:      # the kernel's loads are aligned
+            frames = frames.clone()
+        return require_native().yuv420_patch_embed(
+            frames, wk, bias_f, P, pos_embed, cls_token, out_dtype,
+            int(tile), chroma == "i420", list(YUV_MATRICES[matrix]))
+    return _image_u8_patch_embed(
+        yuv420_to_rgb_u8(frames, chroma, matrix), wk, bias_f, P, pos_embed,
+        cls_token, out_dtype, 0)
 
 
 def masked_mean_pool(hidden, mask=None, normalize=False):

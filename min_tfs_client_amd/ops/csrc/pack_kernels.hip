@@ -47,6 +47,7 @@
 #include <vector>
 
 #include "staging.h"
+#include "yuv420_convert.h"
 
 #define HIP_CHECK(expr)                                                       \
   do {                                                                        \
@@ -905,10 +906,8 @@ u8_ragged_resize_normalize_kernel(
 //  * direct path: Yuv420Row converts per tap from global memory. Taken when
 //    the host found that the tile's spans exceed kResizeLdsBytes (span_px ==
 //    0), or when a tile's span does not fit the estimate.
-struct Yuv420Coef {
-  int yoff, yc, rv, gu, gv, bu;
-};
-
+// Yuv420Coef and yuv_clamp8 (clamp first, never shift-then-clamp) live in
+// yuv420_convert.h, shared with patch_embed.hip.
 struct Yuv420ResizeParams {
   U8ResizeParams r;   // span_stride: LDS bytes per span, 48 per fill chunk
   Yuv420Coef k;
@@ -916,13 +915,6 @@ struct Yuv420ResizeParams {
 };
 
 constexpr int kYuvChunkPx = 16;
-
-// clamp(v >> 8, 0, 255), written clamp first: the same value for every v.
-// The shift-then-clamp form is selected as v_ashr_pk_u8_i32 for pairs of
-// values by hipcc (ROCm 7.2), and the packed bytes came out wrong on MI355X.
-__device__ __forceinline__ uint32_t yuv_clamp8(int v) {
-  return uint32_t(min(max(v, 0), 0xffff)) >> 8;
-}
 
 // One source row in global memory. `u`/`v` point at the row's first chroma
 // sample, `cstep` bytes apart (NV12: 2 with v = u + 1; I420: 1).

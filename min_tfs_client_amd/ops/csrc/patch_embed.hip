@@ -1,7 +1,8 @@
-// CDNA4 (gfx950) fused ViT patch embedding: raw uint8 NHWC pixels in, token
-// matrix out, one launch, matrix cores.
+// CDNA4 (gfx950) fused ViT patch embedding: raw uint8 NHWC pixels, or YUV
+// 4:2:0 frames (NV12 / I420), in, token matrix out, one launch, matrix cores.
 //
 //   images uint8 [N,H,W,3]      wk bf16 [D,Kp]     bias fp32 [D]
+//   (or frames uint8 [N,H*3/2,W], converted to those pixels on the way in)
 //   pos fp32 [T,D] or null      cls fp32 [D] or null
 //   out[n, t0+tok, d] = cvt( sum_k u8(n,tok,k) * wk[d,k] + bias[d] + pos )
 //   out[n, 0, d]      = cvt( cls[d] + pos[0,d] )          (cls given: t0 = 1)
@@ -31,7 +32,16 @@
 // MI355X (ViT-B/16, bf16 out): 8 images (78 large tiles) 19 us small against
 // 39 us large; 32 images (294 large tiles) 67 us small against 49 us large.
 //
-// K loop, kPeBK = 64 bytes of K per step (two MFMA slabs):
+// One kernel body, patch_embed_kernel, and two A loaders (a template
+// parameter: PeRgbLoader, PeYuvLoader). The loader owns the A side of a K
+// step: how many bytes of K a step is (BK), the LDS row stride (STRIDE), the
+// per-row offsets, the global -> register prefetch and the register -> LDS
+// store. The MFMA loop, the B fragments, the epilogue and the class-token
+// rows are written once, so an output element accumulates the same 32-wide K
+// slabs in the same ascending order into one accumulator whatever the loader:
+// tile shape and bytes of K per barrier do not enter that order.
+//
+// K loop of the RGB loader, BK = 64 bytes of K per step (two MFMA slabs):
 //  * A: each thread loads its share of the BM x 64 byte tile from global
 //    memory into registers one step ahead, then stores it to one of two LDS
 //    buffers AS BYTES (a quarter of the LDS traffic of staged bf16). Loads
@@ -41,7 +51,7 @@
 //    every step: rows past M and K positions past K = 3*P*P (the tail up to
 //    Kp, and the rest of the last step) are zeros, never stale LDS, because
 //    garbage widened to bf16 may be Inf/NaN and Inf * 0 is NaN.
-//    The row stride is kPeLdsStride = 80 = 16 * 5 bytes: a fragment read is
+//    The row stride is STRIDE = 80 = 16 * 5 bytes: a fragment read is
 //    8 bytes per lane (row = lane % 16, K offset = 8 * (lane / 16)), and
 //    with an odd number of 16-byte slots per row the 16 rows of a half-wave
 //    fall into 16 different slots of the 64 banks: conflict-free.
@@ -62,6 +72,52 @@
 // token rows are written by the workgroups whose tile holds an image's first
 // token, for their own BN columns: still one launch, every output element is
 // written by exactly one lane, no atomics, no split K: bit-identical reruns.
+//
+// YUV 4:2:0 loader (P = 16 and 32; a 42-byte P = 14 row fits neither the K
+// step nor the loads). Frames are laid out as in the YUV section of
+// pack_kernels.hip and converted with its int32 arithmetic (yuv420_convert.h:
+// Yuv420Coef, clamp-first yuv_clamp8). The converted pixel is a uint8 value,
+// so A stays exact in bf16, wk is the RGB path's tensor (K keeps its
+// (py, px, c) order) and the result is bit-identical to the RGB kernel on the
+// converted frames, which never exist in memory.
+//  * BK = 96 bytes of K per step (three MFMA slabs) = 32 pixels per tile row,
+//    the luma rows that share one chroma row: P = 16: patch rows 2s and 2s+1
+//    with chroma row s of the patch, K = 768 in 8 steps; P = 32: patch row s
+//    with chroma row s >> 1, K = 3072 in 32 steps. Kp = K: no K tail.
+//  * The 32 * BM pixels of a step are 256 work units, one per thread:
+//      BM = 128, P = 16: 8 pixels x 2 luma rows. Loads 2 x 8 B luma and 8 B
+//                        of NV12 pairs / 2 x 4 B of I420; stores 2 x 24 B.
+//      BM = 128, P = 32: 16 pixels x 1 row. Loads 16 B luma and 16 B NV12 /
+//                        2 x 8 B I420; stores 48 B.
+//      BM = 32:          4 pixels x 1 row (all 256 threads convert, chroma is
+//                        read twice for P = 16). Loads 4 B luma and 4 B NV12
+//                        / 2 x 2 B I420; stores 12 B.
+//    A unit is loaded into registers one step ahead, like the RGB loader's,
+//    converted at store time and written to the LDS tile as RGB bytes at its
+//    K offset; the tile stays bytes, widened at the fragment read. H and W
+//    are multiples of 16 and the tensor is 16-byte aligned, so every luma and
+//    chroma offset of a unit is a multiple of its load width in both layouts
+//    (frame: 384 | H*W*3/2; chroma planes: 64 | H*W/4; rows: 8 | W/2), and a
+//    unit lies inside its patch, so no byte outside the tensor is read. Rows
+//    past M load nothing and store zeros on every step (the conversion of
+//    zeros is not zero). Frame bases are int64.
+//  * STRIDE = 112 = 16 * 7 bytes: seven slots, odd, so the fragment reads are
+//    conflict-free by the argument above. Stores, by bank arithmetic (64
+//    banks, a pass is 64 / 32 / 16 lanes of 4 / 8 / 16 B), not counters:
+//    the 8-byte stores of the 128-row P = 16 tile are conflict-free (units
+//    of a row sit 24 B apart: words 0,1 and 2,3 of the row's 16-byte slots);
+//    the 16-byte stores of the 128-row P = 32 tile and the 4-byte stores of
+//    the 32-row tiles are two-way. That is 3 extra store passes per thread
+//    and step, next to 3 * TM fragment reads and 3 * TM * TN MFMAs.
+//  * LDS: 2 x 128 x 112 B + tables = 31 KB (large), 7.8 KB (small). gfx950
+//    resource use (hipcc, ROCm 7.2): large tile 162-168 VGPRs + 64 AGPRs,
+//    small tile 50-52 + 4, no scratch; occupancy 2 / 8 waves per SIMD, as
+//    the RGB instantiations (130-136 + 64, 44 + 4).
+//  * Tiles, the tile rule and the workgroup order are the RGB path's. The
+//    measured crossover is the same (MI355X, ViT-B/16, NV12, bf16 out: 8
+//    images 20 us small against 41 us large; 32 images 65 us small against
+//    49 us large), and the fused op takes 0.93-1.10 of the RGB kernel's time
+//    on converted frames (profiles/README.md).
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
@@ -74,13 +130,14 @@
 #include <stdexcept>
 #include <string>
 #include <type_traits>
+#include <vector>
+
+#include "yuv420_convert.h"
 
 namespace mi355x {
 namespace {
 
 constexpr int kPeThreads = 256;
-constexpr int kPeBK = 64;
-constexpr int kPeLdsStride = 80;
 constexpr int kPeLargeM = 128, kPeLargeN = 128;
 constexpr int kPeSmallM = 32, kPeSmallN = 32;
 constexpr int64_t kPeLargeMinTiles = 256;
@@ -89,7 +146,7 @@ typedef __bf16 pe_bf16x8 __attribute__((ext_vector_type(8)));
 typedef float pe_f32x4 __attribute__((ext_vector_type(4)));
 
 struct PatchEmbedParams {
-  const uint8_t* img;
+  const uint8_t* img;   // RGB pixels, or YUV 4:2:0 frames
   const uint16_t* wk;
   const float* bias;
   const float* pos;   // may be null
@@ -99,6 +156,10 @@ struct PatchEmbedParams {
   int H, W, Wp, HW;   // HW = Hp * Wp
   int D, K, Kp, T, t0;
   int tiles_n;
+  // YUV loaders only
+  int64_t frame;      // bytes of one frame, H*W*3/2
+  int64_t vplane;     // I420: bytes from a U sample to its V, (H/2)*(W/2)
+  Yuv420Coef k;
 };
 
 struct PeOutF32 {
@@ -137,48 +198,45 @@ __device__ __forceinline__ pe_bf16x8 pe_widen8(uint2 v) {
   return u.f;
 }
 
-template <int P, int TM, int TN, typename OUT>
-__global__ void __launch_bounds__(kPeThreads)
-u8_patch_embed_kernel(const PatchEmbedParams p) {
-  constexpr int BM = 32 * TM, BN = 32 * TN;
-  constexpr int VEC = (P % 16 == 0) ? 16 : 2;      // bytes per A load
-  constexpr int ROWB = 3 * P;                      // bytes of one patch row
-  constexpr int UPR = kPeBK / VEC;                 // load units per tile row
-  constexpr int UNITS = BM * UPR;
-  constexpr int UPT = (UNITS + kPeThreads - 1) / kPeThreads;
+// ---------------------------------------------------------------------------
+// A loaders. A loader is one thread's share of the A side of the K loop: the
+// geometry of a step (BK bytes of K, STRIDE bytes per LDS tile row), the
+// offsets kept per tile row, `load(p, s)`: global memory -> registers for
+// step s, and `store(buf)`: registers -> the BM x BK byte tile at `buf`.
+// ---------------------------------------------------------------------------
+
+// RGB: the K bytes of a step are contiguous pixels of one or two patch rows.
+template <int P, int BM_>
+struct PeRgbLoader {
+  static constexpr int BM = BM_, BK = 64, STRIDE = 80;
+  static constexpr bool kChroma = false;
+  static constexpr int VEC = (P % 16 == 0) ? 16 : 2;   // bytes per A load
+  static constexpr int ROWB = 3 * P;                   // bytes of a patch row
+  static constexpr int UPR = BK / VEC;                 // load units per row
+  static constexpr int UNITS = BM * UPR;
+  static constexpr int UPT = (UNITS + kPeThreads - 1) / kPeThreads;
   using AVec = std::conditional_t<VEC == 16, uint4, uint16_t>;
-  using OutT = typename OUT::T;
 
-  __shared__ __attribute__((aligned(16))) uint8_t a_lds[2][BM * kPeLdsStride];
-  __shared__ int64_t row_pix[BM];   // byte offset of the patch's first pixel
-  __shared__ int row_tok[BM];       // token index inside the image, -1: past M
-  __shared__ int row_img[BM];
-
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int lrow = lane & 15, lgrp = lane >> 4;
-  const int tile_n = int(blockIdx.x % uint32_t(p.tiles_n));
-  const int m0 = int(blockIdx.x / uint32_t(p.tiles_n)) * BM;
-  const int d0 = tile_n * BN;
-
-  if (tid < BM) {
-    const int m = m0 + tid;
-    int tok = -1, n = 0;
-    int64_t pix = 0;
-    if (m < p.M) {
-      n = m / p.HW;
-      tok = m - n * p.HW;
-      const int hp = tok / p.Wp, wp = tok - hp * p.Wp;
-      pix = ((int64_t(n) * p.H + int64_t(hp) * P) * p.W + int64_t(wp) * P) * 3;
-    }
-    row_pix[tid] = pix;
-    row_tok[tid] = tok;
-    row_img[tid] = n;
-  }
-  __syncthreads();
-
+  const int64_t* row_pix;
+  const int* row_tok;
+  int tid;
   AVec a_reg[UPT];
-  auto load_a = [&](int k0) {
+
+  // byte offset of the first pixel of patch (hp, wp) of image n
+  static __device__ __forceinline__ void offsets(
+      const PatchEmbedParams& p, int n, int hp, int wp, int64_t& pix,
+      int64_t&) {
+    pix = ((int64_t(n) * p.H + int64_t(hp) * P) * p.W + int64_t(wp) * P) * 3;
+  }
+  __device__ __forceinline__ void init(const PatchEmbedParams&, int tid_,
+                                       const int64_t* pix, const int64_t*,
+                                       const int* tok) {
+    row_pix = pix;
+    row_tok = tok;
+    tid = tid_;
+  }
+  __device__ __forceinline__ void load(const PatchEmbedParams& p, int s) {
+    const int k0 = s * BK;
 #pragma unroll
     for (int i = 0; i < UPT; ++i) {
       const int u = tid + i * kPeThreads;
@@ -196,17 +254,228 @@ u8_patch_embed_kernel(const PatchEmbedParams p) {
       }
       a_reg[i] = v;
     }
-  };
-  auto store_a = [&](int buf) {
+  }
+  __device__ __forceinline__ void store(const PatchEmbedParams&,
+                                        uint8_t* buf) const {
 #pragma unroll
     for (int i = 0; i < UPT; ++i) {
       const int u = tid + i * kPeThreads;
       if (UNITS % kPeThreads == 0 || u < UNITS)
-        *reinterpret_cast<AVec*>(
-            &a_lds[buf][(u / UPR) * kPeLdsStride + (u % UPR) * VEC]) =
+        *reinterpret_cast<AVec*>(&buf[(u / UPR) * STRIDE + (u % UPR) * VEC]) =
             a_reg[i];
     }
-  };
+  }
+};
+
+// NB aligned bytes -> the low bytes of d[0..]
+template <int NB>
+__device__ __forceinline__ void pe_load_bytes(const uint8_t* a, uint32_t* d) {
+  if constexpr (NB == 2) {
+    d[0] = *reinterpret_cast<const uint16_t*>(a);
+  } else if constexpr (NB == 4) {
+    d[0] = *reinterpret_cast<const uint32_t*>(a);
+  } else if constexpr (NB == 8) {
+    const uint2 v = *reinterpret_cast<const uint2*>(a);
+    d[0] = v.x; d[1] = v.y;
+  } else {
+    static_assert(NB == 16, "load width");
+    const uint4 v = *reinterpret_cast<const uint4*>(a);
+    d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+  }
+}
+
+__device__ __forceinline__ int pe_byte(const uint32_t* w, int b) {
+  return int((w[b >> 2] >> (8 * (b & 3))) & 0xffu);
+}
+
+// YUV 4:2:0 (NV12 / I420): a step is 96 bytes of K = 32 pixels per tile row,
+// the luma rows that share ONE chroma row: P = 16: patch rows 2s and 2s+1
+// (chroma row s of the patch), P = 32: patch row s (chroma row s >> 1). The
+// 32 * BM pixels of a step are cut into 256 units, one per thread, of NR luma
+// rows x PX pixels with the chroma pairs below them:
+//   BM = 128, P = 16: 2 x 8     BM = 128, P = 32: 1 x 16     BM = 32: 1 x 4
+// A unit is loaded into registers one step ahead (luma: NR loads of PX bytes;
+// chroma: PX bytes of NV12 pairs, or PX/2 bytes each of U and V), converted
+// in int32 at store time and written as RGB bytes at its K offset.
+template <int P, int BM_, bool I420>
+struct PeYuvLoader {
+  static_assert(P == 16 || P == 32, "a 42-byte patch row fits no unit");
+  static constexpr int BM = BM_, BK = 96, STRIDE = 112;
+  static constexpr bool kChroma = true;
+  static constexpr int UPR = kPeThreads / BM;          // units per tile row
+  static_assert(UPR == 2 || UPR == 8, "one unit per thread");
+  static constexpr int NR = (P == 16 && UPR == 2) ? 2 : 1;
+  static constexpr int PX = 32 / UPR / NR;             // 4, 8 or 16
+  static constexpr int PXW = PX / 4;                   // words of PX bytes
+  static constexpr int LROWS = (P == 16) ? 2 : 1;      // luma rows per step
+
+  const uint8_t* ya;     // luma of the unit at step 0; null: row past M
+  const uint8_t* ua;     // its first U sample (NV12: first (U,V) pair)
+  int lds_off, W;
+  uint32_t y[NR][PXW];
+  uint32_t c[PXW];       // NV12: U,V interleaved; I420: PX/2 U, then PX/2 V
+
+  // luma offset of the first pixel of patch (hp, wp) of frame n, and the
+  // offset of its first chroma sample (I420: in the U plane)
+  static __device__ __forceinline__ void offsets(
+      const PatchEmbedParams& p, int n, int hp, int wp, int64_t& pix,
+      int64_t& chr) {
+    const int64_t fb = int64_t(n) * p.frame;
+    const int64_t crow = int64_t(hp) * (P / 2);
+    pix = fb + int64_t(hp) * P * p.W + int64_t(wp) * P;
+    chr = fb + int64_t(p.H) * p.W +
+          (I420 ? crow * (p.W / 2) + int64_t(wp) * (P / 2)
+                : crow * p.W + int64_t(wp) * P);
+  }
+  __device__ __forceinline__ void init(const PatchEmbedParams& p, int tid,
+                                       const int64_t* row_pix,
+                                       const int64_t* row_chr,
+                                       const int* row_tok) {
+    const int r = tid / UPR, q = tid % UPR;
+    const int kp = q * PX;                             // pixel of K in a step
+    const int j0 = (P == 16) ? kp / 16 : 0, px0 = (P == 16) ? kp % 16 : kp;
+    W = p.W;
+    lds_off = r * STRIDE + kp * 3;
+    ya = ua = nullptr;
+    if (row_tok[r] >= 0) {
+      ya = p.img + row_pix[r] + int64_t(j0) * p.W + px0;
+      ua = p.img + row_chr[r] + (I420 ? px0 / 2 : px0);
+    }
+  }
+  __device__ __forceinline__ void load(const PatchEmbedParams& p, int s) {
+#pragma unroll
+    for (int w = 0; w < PXW; ++w) c[w] = 0;
+#pragma unroll
+    for (int jr = 0; jr < NR; ++jr)
+#pragma unroll
+      for (int w = 0; w < PXW; ++w) y[jr][w] = 0;
+    if (ya == nullptr) return;
+    const int crow = (P == 16) ? s : s >> 1;
+#pragma unroll
+    for (int jr = 0; jr < NR; ++jr)
+      pe_load_bytes<PX>(ya + (int64_t(s) * LROWS + jr) * W, y[jr]);
+    if constexpr (I420) {
+      const uint8_t* u = ua + int64_t(crow) * (W / 2);
+      if constexpr (PX == 4) {
+        uint32_t uu, vv;
+        pe_load_bytes<2>(u, &uu);
+        pe_load_bytes<2>(u + p.vplane, &vv);
+        c[0] = uu | (vv << 16);
+      } else {
+        pe_load_bytes<PX / 2>(u, c);
+        pe_load_bytes<PX / 2>(u + p.vplane, c + PXW / 2);
+      }
+    } else {
+      pe_load_bytes<PX>(ua + int64_t(crow) * W, c);
+    }
+  }
+  __device__ __forceinline__ void store(const PatchEmbedParams& p,
+                                        uint8_t* buf) const {
+    uint32_t o[NR][3 * PXW];
+#pragma unroll
+    for (int jr = 0; jr < NR; ++jr)
+#pragma unroll
+      for (int w = 0; w < 3 * PXW; ++w) o[jr][w] = 0;
+    const Yuv420Coef& k = p.k;
+#pragma unroll
+    for (int pr = 0; pr < PX / 2; ++pr) {
+      const int D = pe_byte(c, I420 ? pr : 2 * pr) - 128;
+      const int E = pe_byte(c, I420 ? PX / 2 + pr : 2 * pr + 1) - 128;
+      const int rE = k.rv * E, gDE = k.gu * D + k.gv * E, bD = k.bu * D;
+#pragma unroll
+      for (int jr = 0; jr < NR; ++jr) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int j = 2 * pr + h;
+          const int base = k.yc * (pe_byte(y[jr], j) - k.yoff) + 128;
+          const uint32_t rgb[3] = {yuv_clamp8(base + rE),
+                                   yuv_clamp8(base + gDE),
+                                   yuv_clamp8(base + bD)};
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch) {
+            const int b = 3 * j + ch;
+            o[jr][b >> 2] |= rgb[ch] << (8 * (b & 3));
+          }
+        }
+      }
+    }
+    // a row past M is zeros, not the conversion of zeros
+    const uint32_t keep = ya != nullptr ? 0xffffffffu : 0u;
+#pragma unroll
+    for (int jr = 0; jr < NR; ++jr) {
+      uint8_t* dst = buf + lds_off + jr * 48;
+#pragma unroll
+      for (int v = 0; v < 3; ++v) {
+        const uint32_t* w = &o[jr][v * PXW];
+        if constexpr (PXW == 1)
+          *reinterpret_cast<uint32_t*>(dst + 4 * v) = w[0] & keep;
+        else if constexpr (PXW == 2)
+          *reinterpret_cast<uint2*>(dst + 8 * v) =
+              uint2{w[0] & keep, w[1] & keep};
+        else
+          *reinterpret_cast<uint4*>(dst + 16 * v) =
+              uint4{w[0] & keep, w[1] & keep, w[2] & keep, w[3] & keep};
+      }
+    }
+  }
+};
+
+template <int P>
+struct PeRgb {
+  template <int BM> using Loader = PeRgbLoader<P, BM>;
+};
+template <int P, bool I420>
+struct PeYuv {
+  template <int BM> using Loader = PeYuvLoader<P, BM, I420>;
+};
+
+// the chroma offsets of the tile rows: LDS only in kernels whose loader asks
+template <int BM>
+__device__ __forceinline__ int64_t* pe_chroma_table() {
+  __shared__ int64_t row_chr[BM];
+  return row_chr;
+}
+
+template <typename LD, int TN, typename OUT>
+__global__ void __launch_bounds__(kPeThreads)
+patch_embed_kernel(const PatchEmbedParams p) {
+  constexpr int BM = LD::BM, TM = BM / 32, BN = 32 * TN;
+  constexpr int KS = LD::BK / 32;                  // MFMA slabs per step
+  using OutT = typename OUT::T;
+
+  __shared__ __attribute__((aligned(16))) uint8_t a_lds[2][BM * LD::STRIDE];
+  __shared__ int64_t row_pix[BM];   // byte offset of the patch's first pixel
+  __shared__ int row_tok[BM];       // token index inside the image, -1: past M
+  __shared__ int row_img[BM];
+  int64_t* row_chr = nullptr;       // offset of the patch's first chroma
+  if constexpr (LD::kChroma) row_chr = pe_chroma_table<BM>();
+
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int lrow = lane & 15, lgrp = lane >> 4;
+  const int tile_n = int(blockIdx.x % uint32_t(p.tiles_n));
+  const int m0 = int(blockIdx.x / uint32_t(p.tiles_n)) * BM;
+  const int d0 = tile_n * BN;
+
+  if (tid < BM) {
+    const int m = m0 + tid;
+    int tok = -1, n = 0;
+    int64_t pix = 0, chr = 0;
+    if (m < p.M) {
+      n = m / p.HW;
+      tok = m - n * p.HW;
+      const int hp = tok / p.Wp, wp = tok - hp * p.Wp;
+      LD::offsets(p, n, hp, wp, pix, chr);
+    }
+    row_pix[tid] = pix;
+    if constexpr (LD::kChroma) row_chr[tid] = chr;
+    row_tok[tid] = tok;
+    row_img[tid] = n;
+  }
+  __syncthreads();
+
+  LD ld;
+  ld.init(p, tid, row_pix, row_chr, row_tok);
 
   // B rows of this lane; a block past D reads row D-1 and is never stored
   const uint16_t* b_row[TN];
@@ -216,10 +485,10 @@ u8_patch_embed_kernel(const PatchEmbedParams p) {
     d = d < p.D ? d : p.D - 1;
     b_row[tn] = p.wk + int64_t(d) * p.Kp + lgrp * 8;
   }
-  uint4 b_next[2][TN], b_cur[2][TN];
+  uint4 b_next[KS][TN], b_cur[KS][TN];
   auto load_b = [&](int k0) {
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
+    for (int ks = 0; ks < KS; ++ks) {
       const int k = k0 + ks * 32;
 #pragma unroll
       for (int tn = 0; tn < TN; ++tn)
@@ -235,31 +504,31 @@ u8_patch_embed_kernel(const PatchEmbedParams p) {
 #pragma unroll
     for (int tn = 0; tn < TN; ++tn) acc[tm][tn] = pe_f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int steps = (p.Kp + kPeBK - 1) / kPeBK;
-  load_a(0);
+  const int steps = (p.Kp + LD::BK - 1) / LD::BK;
+  ld.load(p, 0);
   load_b(0);
   for (int s = 0; s < steps; ++s) {
     const int buf = s & 1;
-    store_a(buf);
+    ld.store(p, a_lds[buf]);
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
+    for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
       for (int tn = 0; tn < TN; ++tn) b_cur[ks][tn] = b_next[ks][tn];
     // one barrier per step: buffer buf was last read two steps ago, and
     // every thread has passed the barrier of the step in between
     __syncthreads();
     if (s + 1 < steps) {
-      load_a((s + 1) * kPeBK);
-      load_b((s + 1) * kPeBK);
+      ld.load(p, s + 1);
+      load_b((s + 1) * LD::BK);
     }
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
+    for (int ks = 0; ks < KS; ++ks) {
       pe_bf16x8 a[TM];
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm) {
         const int r = (wm * TM + tm) * 16 + lrow;
         a[tm] = pe_widen8(*reinterpret_cast<const uint2*>(
-            &a_lds[buf][r * kPeLdsStride + ks * 32 + lgrp * 8]));
+            &a_lds[buf][r * LD::STRIDE + ks * 32 + lgrp * 8]));
       }
 #pragma unroll
       for (int tn = 0; tn < TN; ++tn) {
@@ -308,66 +577,60 @@ u8_patch_embed_kernel(const PatchEmbedParams p) {
   }
 }
 
-template <int P, int TM, int TN, typename OUT>
+template <typename LD, int TN, typename OUT>
 void launch_patch_embed(const PatchEmbedParams& p, int64_t tiles,
                         hipStream_t stream) {
-  hipLaunchKernelGGL((u8_patch_embed_kernel<P, TM, TN, OUT>),
+  hipLaunchKernelGGL((patch_embed_kernel<LD, TN, OUT>),
                      dim3(uint32_t(tiles)), dim3(kPeThreads), 0, stream, p);
 }
 
-template <int P, int TM, int TN>
+template <typename LD, int TN>
 void launch_patch_embed_out(at::ScalarType out_dtype,
                             const PatchEmbedParams& p, int64_t tiles,
                             hipStream_t stream) {
   if (out_dtype == at::kFloat)
-    launch_patch_embed<P, TM, TN, PeOutF32>(p, tiles, stream);
+    launch_patch_embed<LD, TN, PeOutF32>(p, tiles, stream);
   else if (out_dtype == at::kBFloat16)
-    launch_patch_embed<P, TM, TN, PeOutBf16>(p, tiles, stream);
+    launch_patch_embed<LD, TN, PeOutBf16>(p, tiles, stream);
   else
-    launch_patch_embed<P, TM, TN, PeOutF16>(p, tiles, stream);
+    launch_patch_embed<LD, TN, PeOutF16>(p, tiles, stream);
 }
 
-template <int P>
+// SRC: PeRgb<P> or PeYuv<P, I420>
+template <typename SRC>
 void launch_patch_embed_tile(bool large, at::ScalarType out_dtype,
                              const PatchEmbedParams& p, int64_t tiles,
                              hipStream_t stream) {
   if (large)
-    launch_patch_embed_out<P, kPeLargeM / 32, kPeLargeN / 32>(
-        out_dtype, p, tiles, stream);
+    launch_patch_embed_out<typename SRC::template Loader<kPeLargeM>,
+                           kPeLargeN / 32>(out_dtype, p, tiles, stream);
   else
-    launch_patch_embed_out<P, kPeSmallM / 32, kPeSmallN / 32>(
-        out_dtype, p, tiles, stream);
+    launch_patch_embed_out<typename SRC::template Loader<kPeSmallM>,
+                           kPeSmallN / 32>(out_dtype, p, tiles, stream);
 }
 
-}  // namespace
+enum class PeSource { kRgb, kNv12, kI420 };
 
-// Fused ViT patch embedding, see the header of this file. ``tile``: 0 picks
-// by the rule there, 1 forces the small tile, 2 the large one (tests reach
-// both at small shapes). Arguments the kernel cannot serve are ValueError.
-at::Tensor u8_patch_embed(const at::Tensor& images, const at::Tensor& wk,
-                          const at::Tensor& bias, int64_t patch,
-                          const c10::optional<at::Tensor>& pos,
-                          const c10::optional<at::Tensor>& cls,
-                          at::ScalarType out_dtype, int64_t tile) {
-  const char* who = "u8_patch_embed";
-  TORCH_CHECK_VALUE(images.is_cuda() && images.dim() == 4 &&
-                    images.is_contiguous() &&
-                    images.scalar_type() == at::kByte && images.size(3) == 3,
-                    who, " expects a contiguous uint8 device tensor [N,H,W,3]");
-  TORCH_CHECK_VALUE(patch == 14 || patch == 16 || patch == 32, who,
-                    ": patch must be 14, 16 or 32, got ", patch);
+// The part of the two entry points below that does not depend on the pixel
+// format: `in` holds N images of H x W pixels and was checked by the caller.
+at::Tensor patch_embed_run(const char* who, const at::Tensor& in,
+                           PeSource src, const Yuv420Coef& coef, int64_t N,
+                           int64_t H, int64_t W, const at::Tensor& wk,
+                           const at::Tensor& bias, int64_t patch,
+                           const c10::optional<at::Tensor>& pos,
+                           const c10::optional<at::Tensor>& cls,
+                           at::ScalarType out_dtype, int64_t tile) {
   TORCH_CHECK_VALUE(out_dtype == at::kFloat || out_dtype == at::kBFloat16 ||
                     out_dtype == at::kHalf,
                     who, ": out_dtype must be f32, bf16 or f16");
   TORCH_CHECK_VALUE(tile >= 0 && tile <= 2, who, ": tile must be 0, 1 or 2");
-  const int64_t N = images.size(0), H = images.size(1), W = images.size(2);
   TORCH_CHECK_VALUE(H >= patch && W >= patch && H % patch == 0 &&
                     W % patch == 0, who, ": H and W must be positive "
                     "multiples of patch ", patch, ", got ", H, "x", W);
   const int64_t Hp = H / patch, Wp = W / patch, HW = Hp * Wp, M = N * HW;
   const int64_t K = 3 * patch * patch, Kp = (K + 31) / 32 * 32;
   auto on_device = [&](const at::Tensor& t) {
-    return t.is_cuda() && t.get_device() == images.get_device() &&
+    return t.is_cuda() && t.get_device() == in.get_device() &&
            t.is_contiguous();
   };
   TORCH_CHECK_VALUE(on_device(wk) && wk.scalar_type() == at::kBFloat16 &&
@@ -391,13 +654,14 @@ at::Tensor u8_patch_embed(const at::Tensor& images, const at::Tensor& wk,
   TORCH_CHECK_VALUE(M <= std::numeric_limits<int32_t>::max() - kPeLargeM &&
                     D <= (1 << 20) && H <= (1 << 20) && W <= (1 << 20), who,
                     ": too many tokens or too large a side");
-  // 16-byte loads of pixels (P = 16, 32) and of weight fragments
+  // 16-byte loads of pixels (P = 16, 32) and of weight fragments; the YUV
+  // units' narrower loads are aligned to their width when the frames are
   TORCH_CHECK_VALUE(
-      reinterpret_cast<uintptr_t>(images.const_data_ptr()) % 16 == 0 &&
+      reinterpret_cast<uintptr_t>(in.const_data_ptr()) % 16 == 0 &&
       reinterpret_cast<uintptr_t>(wk.const_data_ptr()) % 16 == 0, who,
       ": images and wk must be 16-byte aligned");
 
-  auto out = at::empty({N, T, D}, images.options().dtype(out_dtype));
+  auto out = at::empty({N, T, D}, in.options().dtype(out_dtype));
   if (N == 0) return out;                 // zero grid: never launch
 
   auto tiles_of = [&](int64_t bm, int64_t bn) {
@@ -412,7 +676,7 @@ at::Tensor u8_patch_embed(const at::Tensor& images, const at::Tensor& wk,
                     ": too many tiles");
 
   PatchEmbedParams p;
-  p.img = static_cast<const uint8_t*>(images.const_data_ptr());
+  p.img = static_cast<const uint8_t*>(in.const_data_ptr());
   p.wk = static_cast<const uint16_t*>(wk.const_data_ptr());
   p.bias = static_cast<const float*>(bias.const_data_ptr());
   p.pos = pos.has_value()
@@ -424,19 +688,97 @@ at::Tensor u8_patch_embed(const at::Tensor& images, const at::Tensor& wk,
   p.H = int(H); p.W = int(W); p.Wp = int(Wp); p.HW = int(HW);
   p.D = int(D); p.K = int(K); p.Kp = int(Kp); p.T = int(T); p.t0 = int(t0);
   p.tiles_n = int((D + bn - 1) / bn);
+  p.frame = H * W * 3 / 2;
+  p.vplane = (H / 2) * (W / 2);
+  p.k = coef;
 
   hipStream_t stream = at::hip::getCurrentHIPStream().stream();
-  if (patch == 14)
-    launch_patch_embed_tile<14>(large, out_dtype, p, tiles, stream);
-  else if (patch == 16)
-    launch_patch_embed_tile<16>(large, out_dtype, p, tiles, stream);
-  else
-    launch_patch_embed_tile<32>(large, out_dtype, p, tiles, stream);
+  const bool p16 = patch == 16;
+  if (src == PeSource::kNv12) {
+    if (p16)
+      launch_patch_embed_tile<PeYuv<16, false>>(large, out_dtype, p, tiles,
+                                                stream);
+    else
+      launch_patch_embed_tile<PeYuv<32, false>>(large, out_dtype, p, tiles,
+                                                stream);
+  } else if (src == PeSource::kI420) {
+    if (p16)
+      launch_patch_embed_tile<PeYuv<16, true>>(large, out_dtype, p, tiles,
+                                               stream);
+    else
+      launch_patch_embed_tile<PeYuv<32, true>>(large, out_dtype, p, tiles,
+                                               stream);
+  } else if (patch == 14) {
+    launch_patch_embed_tile<PeRgb<14>>(large, out_dtype, p, tiles, stream);
+  } else if (p16) {
+    launch_patch_embed_tile<PeRgb<16>>(large, out_dtype, p, tiles, stream);
+  } else {
+    launch_patch_embed_tile<PeRgb<32>>(large, out_dtype, p, tiles, stream);
+  }
   hipError_t err = hipGetLastError();
   if (err != hipSuccess)
     throw std::runtime_error(std::string("HIP error: ") +
-                             hipGetErrorString(err) + " at u8_patch_embed");
+                             hipGetErrorString(err) + " at " + who);
   return out;
+}
+
+}  // namespace
+
+// Fused ViT patch embedding, see the header of this file. ``tile``: 0 picks
+// by the rule there, 1 forces the small tile, 2 the large one (tests reach
+// both at small shapes). Arguments the kernel cannot serve are ValueError.
+at::Tensor u8_patch_embed(const at::Tensor& images, const at::Tensor& wk,
+                          const at::Tensor& bias, int64_t patch,
+                          const c10::optional<at::Tensor>& pos,
+                          const c10::optional<at::Tensor>& cls,
+                          at::ScalarType out_dtype, int64_t tile) {
+  const char* who = "u8_patch_embed";
+  TORCH_CHECK_VALUE(images.is_cuda() && images.dim() == 4 &&
+                    images.is_contiguous() &&
+                    images.scalar_type() == at::kByte && images.size(3) == 3,
+                    who, " expects a contiguous uint8 device tensor [N,H,W,3]");
+  TORCH_CHECK_VALUE(patch == 14 || patch == 16 || patch == 32, who,
+                    ": patch must be 14, 16 or 32, got ", patch);
+  return patch_embed_run(who, images, PeSource::kRgb, Yuv420Coef{},
+                         images.size(0), images.size(1), images.size(2), wk,
+                         bias, patch, pos, cls, out_dtype, tile);
+}
+
+// The same from YUV 4:2:0 frames: ``frames`` is uint8 [N, H*3/2, W], NV12 or
+// (``i420``) I420 as laid out in the YUV section of pack_kernels.hip, and
+// ``coef`` is (yoff, yc, rv, gu, gv, bu) of the int32 conversion. The result
+// is bit-identical to u8_patch_embed on the converted RGB frames, which never
+// exist in memory. Patches are 16 and 32.
+at::Tensor yuv420_patch_embed(const at::Tensor& frames, const at::Tensor& wk,
+                              const at::Tensor& bias, int64_t patch,
+                              const c10::optional<at::Tensor>& pos,
+                              const c10::optional<at::Tensor>& cls,
+                              at::ScalarType out_dtype, int64_t tile,
+                              bool i420, std::vector<int64_t> coef) {
+  const char* who = "yuv420_patch_embed";
+  constexpr int64_t kMaxSide = 16384;
+  TORCH_CHECK_VALUE(frames.is_cuda() && frames.dim() == 3 &&
+                    frames.is_contiguous() &&
+                    frames.scalar_type() == at::kByte,
+                    who, " expects a contiguous uint8 device tensor "
+                    "[N,H*3/2,W]");
+  TORCH_CHECK_VALUE(patch == 16 || patch == 32, who,
+                    ": patch must be 16 or 32, got ", patch);
+  TORCH_CHECK_VALUE(frames.size(1) % 3 == 0, who,
+                    ": rows must be a multiple of 3");
+  const int64_t H = frames.size(1) / 3 * 2, W = frames.size(2);
+  TORCH_CHECK_VALUE(H >= 2 && H <= kMaxSide && W >= 2 && W <= kMaxSide &&
+                    H % 2 == 0 && W % 2 == 0, who,
+                    ": frame sides must be even and in 2..16384");
+  TORCH_CHECK_VALUE(coef.size() == 6, who, ": coef needs 6 values");
+  for (int64_t v : coef)   // sums stay far inside int32
+    TORCH_CHECK_VALUE(v >= -4096 && v <= 4096, who,
+                      ": coefficient out of range");
+  const Yuv420Coef k{int(coef[0]), int(coef[1]), int(coef[2]), int(coef[3]),
+                     int(coef[4]), int(coef[5])};
+  return patch_embed_run(who, frames, i420 ? PeSource::kI420 : PeSource::kNv12,
+                         k, frames.size(0), H, W, wk, bias, patch, pos, cls,
+                         out_dtype, tile);
 }
 
 }  // namespace mi355x

@@ -22,7 +22,9 @@ one batch; ``AntialiasedRaggedImagePreprocess`` does the same with the
 antialiased filter, in two launches.
 ``PatchEmbedPreprocess`` is the Vision Transformer case: uint8 pixels go
 straight to encoder tokens, normalization, patch projection, class token and
-position embedding in one matrix-core kernel (``ops.image_u8_patch_embed``).
+position embedding in one matrix-core kernel (``ops.image_u8_patch_embed``);
+``Yuv420PatchEmbedPreprocess`` feeds the same kernel NV12 or I420 frames,
+converted while the tile is filled (``ops.image_yuv420_patch_embed``).
 """
 from __future__ import annotations
 
@@ -418,6 +420,46 @@ class PatchEmbedPreprocess:
         return ops.image_u8_patch_embed(
             x, wk, bias_f, self.patch, pos_embed=pos, cls_token=cls,
             out_dtype=self.out_dtype)
+
+
+class Yuv420PatchEmbedPreprocess(PatchEmbedPreprocess):
+    """uint8 ``[N,H*3/2,W]`` YUV 4:2:0 frames -> ViT tokens ``[N,T,D]``:
+    the conversion to RGB happens inside the patch-embedding kernel
+    (``ops.image_yuv420_patch_embed``), from half the request bytes.
+
+    ``chroma`` (``"nv12"`` or ``"i420"``) and ``matrix`` are those of
+    ``ops.yuv420_to_rgb_u8``; everything else, the lazy refold included, is
+    :class:`PatchEmbedPreprocess`, and the tokens are exactly what that class
+    gives for the converted RGB frames, bit for bit. The patch is 16 or 32."""
+
+    def __init__(self, weight, bias, mean, std, pos_embed=None,
+                 cls_token=None, out_dtype=None,
+                 pixel_scale: float = 1.0 / 255.0, device=None,
+                 chroma: str = "nv12", matrix: str = "bt601"):
+        super().__init__(weight, bias, mean, std, pos_embed=pos_embed,
+                         cls_token=cls_token, out_dtype=out_dtype,
+                         pixel_scale=pixel_scale, device=device)
+        if self.patch not in ops.YUV420_PATCH_EMBED_PATCHES:
+            raise ValueError(
+                f"patch must be one of {ops.YUV420_PATCH_EMBED_PATCHES} for "
+                f"YUV 4:2:0 input, got {self.patch}")
+        if chroma not in ops.YUV_CHROMA_LAYOUTS:
+            raise ValueError(
+                f"chroma must be 'nv12' or 'i420', got {chroma!r}")
+        if matrix not in ops.YUV_MATRICES:
+            raise ValueError(
+                f"matrix must be one of {sorted(ops.YUV_MATRICES)}, got "
+                f"{matrix!r}")
+        self.chroma, self.matrix = chroma, matrix
+
+    def __call__(self, x):
+        x = _as_tensor(x)
+        if self.device is not None and x.dtype == torch.uint8:
+            x = x.to(self.device)
+        wk, bias_f, pos, cls = self.folded()
+        return ops.image_yuv420_patch_embed(
+            x, wk, bias_f, self.patch, pos_embed=pos, cls_token=cls,
+            out_dtype=self.out_dtype, chroma=self.chroma, matrix=self.matrix)
 
 
 def pack_ragged_images(images):

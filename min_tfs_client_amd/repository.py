@@ -33,10 +33,13 @@ On-disk version-directory formats understood by the default loader:
                                "sentence_embedding"), "top_k" (resnet50,
                                with "topk": 1..64 classes per image) and
                                "normalize_embedding" (bert_base); vit_b16
-                               takes "input_format" ("float_nchw" or
+                               takes "input_format" ("float_nchw",
                                "uint8_nhwc": raw pixels into the fused
-                               patch-embedding kernel), "output_format"
-                               ("logits" or "topk") and "top_k"
+                               patch-embedding kernel, or "nv12" / "i420":
+                               YUV 4:2:0 frames into the same kernel),
+                               "yuv_matrix" (with the YUV modes),
+                               "output_format" ("logits" or "topk") and
+                               "top_k"
   * ``model.pt``            — TorchScript module (torch.jit.load)
 plus TF-style ``assets.extra/tf_serving_warmup_requests`` (a TFRecord of
 serialized PredictionLog protos — framing per TF's RecordWriter: length,
@@ -199,7 +202,8 @@ def default_loader(name: str, version_dir: str,
         elif family == "vit_b16":
             from .models import vit_b16_servable
             modes = {k: cfg[k]
-                     for k in ("input_format", "output_format", "top_k")
+                     for k in ("input_format", "output_format", "top_k",
+                               "yuv_matrix")
                      if k in cfg}
             servable = vit_b16_servable(device, **modes)
         elif family == "identity":

@@ -3,6 +3,7 @@
 composed chain a user would run without it, one GPU.
 
     python tools/bench_patch_embed.py          # JSON lines
+    python tools/bench_patch_embed.py --yuv    # NV12 / I420 input, see below
 
 The parent process never touches the GPU; the timings run in one fresh child
 process under a time limit, and the tool exits non-zero if it fails.
@@ -21,6 +22,18 @@ pixels in, tokens out, weights once (15.7 MB for 32 images in bf16, 1.2 MB
 of it weights).
 ``max_abs_diff`` against the baseline is reported, not asserted: the
 baseline rounds the normalized pixel and the weights differently.
+
+``--yuv``: ``ops.image_yuv420_patch_embed`` on NV12 and I420 frames, bf16
+output, the same shapes and batches, per tile (rule, small, large):
+
+    (a) ``yuv_*_ms``       the fused YUV op
+    (b) ``rgb_*_ms``       the RGB kernel on an already converted tensor, the
+                           floor: (a)/(b) is the cost of converting inside
+    (c) ``two_step_*_ms``  what a user runs without it: ``yuv420_to_rgb_u8``
+                           on the device, then the RGB kernel
+
+with the ratios (a)/(b) and (c)/(a), and ``identical``: whether (a) and (c)
+gave the same bits.
 """
 import json
 import os
@@ -105,10 +118,69 @@ def run_cases():
             print(json.dumps(row), flush=True)
 
 
+def run_yuv_cases():
+    import torch
+
+    from min_tfs_client_amd import ops
+    from min_tfs_client_amd.preprocess import IMAGENET_MEAN, IMAGENET_STD
+
+    dev, P, D, S = "cuda:0", 16, 768, 224
+    T = (S // P) ** 2 + 1
+    dtype = torch.bfloat16
+    g = torch.Generator().manual_seed(0)
+    w = torch.randn((D, 3, P, P), generator=g) * 0.02
+    b = torch.randn(D, generator=g) * 0.02
+    pos = (torch.randn((T, D), generator=g) * 0.02).to(dev)
+    cls = (torch.randn(D, generator=g) * 0.02).to(dev)
+    wk, bias_f = (t.to(dev) for t in ops.patch_embed_fold(
+        w, b, IMAGENET_MEAN, IMAGENET_STD))
+    for chroma in ops.YUV_CHROMA_LAYOUTS:
+        for N in BATCHES:
+            x = torch.randint(0, 256, (N, S * 3 // 2, S), dtype=torch.uint8,
+                              generator=g).to(dev)
+            rgb = ops.yuv420_to_rgb_u8(x, chroma)
+
+            def yuv(tile):
+                return ops._image_yuv420_patch_embed(
+                    x, wk, bias_f, P, pos, cls, dtype, tile, chroma=chroma)
+
+            def floor(tile):
+                return ops._image_u8_patch_embed(
+                    rgb, wk, bias_f, P, pos, cls, dtype, tile)
+
+            def two_step(tile):
+                return ops._image_u8_patch_embed(
+                    ops.yuv420_to_rgb_u8(x, chroma), wk, bias_f, P, pos, cls,
+                    dtype, tile)
+
+            same = all(torch.equal(yuv(t), two_step(t))
+                       for t in TILES.values())
+            reps = 200 if N <= 32 else 50
+            fns = [lambda f=f, t=t: f(t) for t in TILES.values()
+                   for f in (yuv, floor, two_step)]
+            rounds = [[time_kernel(f, reps, 10) for f in fns]
+                      for _ in range(5)]
+            ms = [sorted(r[i] for r in rounds)[2] for i in range(len(fns))]
+            row = {"case": f"{N}x{S}x{S}_{chroma}_bfloat16",
+                   "identical": same}
+            for i, name in enumerate(TILES):
+                a, fl, c = ms[3 * i:3 * i + 3]
+                row.update({
+                    f"yuv_{name}_ms": round(a, 4),
+                    f"rgb_{name}_ms": round(fl, 4),
+                    f"two_step_{name}_ms": round(c, 4),
+                    f"yuv_over_rgb_{name}": round(a / fl, 2),
+                    f"two_step_over_yuv_{name}": round(c / a, 2)})
+            print(json.dumps(row), flush=True)
+
+
 def main():
     if sys.argv[1:] == ["--cases"]:
         return run_cases()
-    cmd = [sys.executable, os.path.abspath(__file__), "--cases"]
+    if sys.argv[1:] == ["--yuv-cases"]:
+        return run_yuv_cases()
+    child = "--yuv-cases" if sys.argv[1:] == ["--yuv"] else "--cases"
+    cmd = [sys.executable, os.path.abspath(__file__), child]
     try:
         rc = subprocess.run(cmd, timeout=TIMEOUT_S).returncode
     except subprocess.TimeoutExpired:
