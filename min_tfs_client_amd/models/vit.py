@@ -14,6 +14,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..preprocess import (IMAGENET_MEAN, IMAGENET_STD, PatchEmbedPreprocess,
+                          ResizePatchEmbedPreprocess,
                           Yuv420PatchEmbedPreprocess)
 
 
@@ -124,6 +125,19 @@ def vit_b16_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
     ``ops.image_yuv420_patch_embed``): the logits are exactly those of
     ``uint8_nhwc`` on the converted frames. The patch must be 16 or 32. A
     non-default ``yuv_matrix`` is rejected in every other mode.
+    ``input_format="uint8_nhwc_resize"``: "images" is DT_UINT8 (N,H,W,3) raw
+    pixels of any size (every image of one request has the same size;
+    requests may differ), as ``resnet50_servable`` takes them: the shorter
+    side is resized to ``image_size * 8 // 7`` (256 for 224, bilinear, no
+    antialiasing), then a centre crop of ``image_size``, both inside the same
+    kernel while it fills its tile (``preprocess.ResizePatchEmbedPreprocess``,
+    ``ops.image_u8_resize_patch_embed``); the model runs ``forward_tokens``.
+    The resized pixel is an fp32 blend and reaches the matrix cores as two
+    bf16 pieces, within 2^-16 of its value. The patch must be 16 or 32.
+    On an MI355X the one launch measured faster than resize-then-embed at
+    every batch and source size tried (profiles/README.md); images that
+    already are ``image_size`` square are served faster by ``uint8_nhwc``
+    (the resampling loader costs 1.6-2.0x there).
 
     ``output_format="logits"`` / ``"topk"`` and ``top_k``: as for
     ``resnet50_servable`` (``postprocess.TopKClassification``).
@@ -132,10 +146,11 @@ def vit_b16_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
     from ..postprocess import TopKClassification
     from ..server import Servable
 
-    if input_format not in ("float_nchw", "uint8_nhwc", "nv12", "i420"):
+    if input_format not in ("float_nchw", "uint8_nhwc", "uint8_nhwc_resize",
+                            "nv12", "i420"):
         raise ValueError(
-            f"input_format must be 'float_nchw', 'uint8_nhwc', 'nv12' or "
-            f"'i420', got {input_format!r}")
+            f"input_format must be 'float_nchw', 'uint8_nhwc', "
+            f"'uint8_nhwc_resize', 'nv12' or 'i420', got {input_format!r}")
     yuv = input_format in ("nv12", "i420")
     if yuv_matrix != "bt601" and not yuv:
         raise ValueError(
@@ -149,7 +164,9 @@ def vit_b16_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
     # top_k is validated in every mode: a typo must not wait for "topk"
     postprocess = TopKClassification(top_k)
     cfg = VitConfig() if config is None else config
-    u8 = input_format == "uint8_nhwc" or yuv      # tokens from the kernel
+    resize = input_format == "uint8_nhwc_resize"
+    # tokens from the kernel
+    u8 = input_format == "uint8_nhwc" or resize or yuv
 
     torch.manual_seed(seed)
     model = vit_b16(cfg).to(device=device, dtype=dtype).eval()
@@ -174,6 +191,13 @@ def vit_b16_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
             IMAGENET_STD, pos_embed=model.pos_embed,
             cls_token=model.cls_token, out_dtype=dtype, device=device,
             chroma=input_format, matrix=yuv_matrix)}
+    elif resize:
+        images_sig = (4, [-1, -1, -1, 3])                   # DT_UINT8
+        preprocess = {"images": ResizePatchEmbedPreprocess(
+            model.patch_embed.weight, model.patch_embed.bias, IMAGENET_MEAN,
+            IMAGENET_STD, pos_embed=model.pos_embed,
+            cls_token=model.cls_token, out_dtype=dtype, device=device,
+            resize=size * 8 // 7, center_crop=size)}
     elif u8:
         images_sig = (4, [-1, size, size, 3])               # DT_UINT8
         preprocess = {"images": PatchEmbedPreprocess(

@@ -224,6 +224,40 @@ def _resize_aa_eager(p, rh, rw, top, left, Hc, Wc):
     return acc / tot.view(1, Hc, 1, 1)
 
 
+def _resize_window(name, Hin, Win, size, crop):
+    """The ``size`` / ``crop`` checks of the ops that resize ``Hin x Win``
+    images: ``(Hr, Wr, top, left, Hc, Wc, rh, rw)``, the ratios rounded once
+    to fp32."""
+    import numpy as np
+
+    try:
+        Hr, Wr = (int(d) for d in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"size must be (H, W), got {size!r}") from None
+    for label, v in (("input height", Hin), ("input width", Win),
+                     ("resized height", Hr), ("resized width", Wr)):
+        if not 1 <= v <= RESIZE_MAX_SIDE:
+            raise ValueError(
+                f"{name}: {label} must be in 1..{RESIZE_MAX_SIDE}, got {v}")
+    if crop is None:
+        top, left, Hc, Wc = 0, 0, Hr, Wr
+    else:
+        try:
+            top, left, Hc, Wc = (int(d) for d in crop)
+        except (TypeError, ValueError):
+            raise ValueError(
+                f"crop must be (top, left, height, width), got {crop!r}"
+            ) from None
+        if Hc < 1 or Wc < 1:
+            raise ValueError(f"crop extent must be positive, got {Hc}x{Wc}")
+        if top < 0 or left < 0 or top + Hc > Hr or left + Wc > Wr:
+            raise ValueError(
+                f"crop window (top={top}, left={left}, {Hc}x{Wc}) is not "
+                f"inside the resized image {Hr}x{Wr}")
+    return (Hr, Wr, top, left, Hc, Wc, float(np.float32(Hin / Hr)),
+            float(np.float32(Win / Wr)))
+
+
 def image_u8_resize_to_float(tensor, size, mean, std, crop=None,
                              out_dtype=None, layout="nchw",
                              pixel_scale=1.0 / 255.0, _variant=0, *,
@@ -285,8 +319,6 @@ def image_u8_resize_to_float(tensor, size, mean, std, crop=None,
     bit-identical and CPU-only servers work too. All sides (``Hin``, ``Win``,
     ``Hr``, ``Wr``) must be in 1..16384. Invalid arguments raise
     ``ValueError`` on both paths; ``N == 0`` returns an empty tensor."""
-    import numpy as np
-
     name = "image_u8_resize_to_float"
     if out_dtype is None:
         out_dtype = torch.float32
@@ -311,33 +343,9 @@ def image_u8_resize_to_float(tensor, size, mean, std, crop=None,
         raise ValueError(
             f"mean/std need {C} entries (one per channel), got "
             f"{len(mean)}/{len(std)}")
-    try:
-        Hr, Wr = (int(d) for d in size)
-    except (TypeError, ValueError):
-        raise ValueError(f"size must be (H, W), got {size!r}") from None
-    for label, v in (("input height", Hin), ("input width", Win),
-                     ("resized height", Hr), ("resized width", Wr)):
-        if not 1 <= v <= RESIZE_MAX_SIDE:
-            raise ValueError(
-                f"{name}: {label} must be in 1..{RESIZE_MAX_SIDE}, got {v}")
-    if crop is None:
-        top, left, Hc, Wc = 0, 0, Hr, Wr
-    else:
-        try:
-            top, left, Hc, Wc = (int(d) for d in crop)
-        except (TypeError, ValueError):
-            raise ValueError(
-                f"crop must be (top, left, height, width), got {crop!r}"
-            ) from None
-        if Hc < 1 or Wc < 1:
-            raise ValueError(f"crop extent must be positive, got {Hc}x{Wc}")
-        if top < 0 or left < 0 or top + Hc > Hr or left + Wc > Wr:
-            raise ValueError(
-                f"crop window (top={top}, left={left}, {Hc}x{Wc}) is not "
-                f"inside the resized image {Hr}x{Wr}")
+    Hr, Wr, top, left, Hc, Wc, rh, rw = _resize_window(
+        name, Hin, Win, size, crop)
     scale, bias = normalization_constants(mean, std, pixel_scale)
-    rh = float(np.float32(Hin / Hr))
-    rw = float(np.float32(Win / Wr))
     if tensor.is_cuda and antialias:
         return require_native().u8_nhwc_resize_aa_normalize(
             tensor, rh, rw, top, left, Hc, Wc, scale, bias, out_dtype,
@@ -861,15 +869,7 @@ def _image_u8_patch_embed(images, wk, bias_f, patch, pos_embed, cls_token,
         raise ValueError(
             f"patch must be one of {PATCH_EMBED_PATCHES}, got {patch!r}")
     P = int(patch)
-    if not isinstance(images, torch.Tensor):
-        raise ValueError(f"{name} expects a torch tensor")
-    if images.dtype != torch.uint8:
-        raise ValueError(f"{name} expects uint8 pixels, got {images.dtype}")
-    if images.dim() != 4:
-        raise ValueError(f"{name} expects [N,H,W,3], got rank {images.dim()}")
-    N, H, W, C = (int(d) for d in images.shape)
-    if C != 3:
-        raise ValueError(f"{name} expects 3 channels, got {C}")
+    N, H, W = _patch_embed_images(name, images)
     out_dtype, T, D = _patch_embed_operands(
         name, images, H, W, P, wk, bias_f, pos_embed, cls_token, out_dtype)
     if N == 0:
@@ -880,13 +880,34 @@ def _image_u8_patch_embed(images, wk, bias_f, patch, pos_embed, cls_token,
         return require_native().u8_patch_embed(
             images, wk, bias_f, P, pos_embed, cls_token, out_dtype,
             int(tile))
-    K, t0 = 3 * P * P, T - (H // P) * (W // P)
-    Hp, Wp = H // P, W // P
-    a = images.view(N, Hp, P, Wp, P, 3).permute(0, 1, 3, 2, 4, 5).reshape(
-        N * Hp * Wp, K).float()
+    return _patch_embed_eager(images.float(), wk, bias_f, P, pos_embed,
+                              cls_token, out_dtype)
+
+
+def _patch_embed_images(name, images):
+    """``(N, H, W)`` of a uint8 ``[N,H,W,3]`` batch, or ``ValueError``."""
+    if not isinstance(images, torch.Tensor):
+        raise ValueError(f"{name} expects a torch tensor")
+    if images.dtype != torch.uint8:
+        raise ValueError(f"{name} expects uint8 pixels, got {images.dtype}")
+    if images.dim() != 4:
+        raise ValueError(f"{name} expects [N,H,W,3], got rank {images.dim()}")
+    N, H, W, C = (int(d) for d in images.shape)
+    if C != 3:
+        raise ValueError(f"{name} expects 3 channels, got {C}")
+    return N, H, W
+
+
+def _patch_embed_eager(a, wk, bias_f, P, pos_embed, cls_token, out_dtype):
+    """The CPU expression of the patch embedding for an fp32 operand ``a``
+    ``[N,H,W,3]``: fp32 matmul, then the kernel's epilogue."""
+    N, H, W, _ = a.shape
+    K, Hp, Wp, D = 3 * P * P, H // P, W // P, wk.shape[0]
+    a = a.view(N, Hp, P, Wp, P, 3).permute(0, 1, 3, 2, 4, 5).reshape(
+        N * Hp * Wp, K)
     y = ((a @ wk[:, :K].float().t()) + bias_f).view(N, Hp * Wp, D)
     if pos_embed is not None:
-        y = y + pos_embed[t0:]
+        y = y + pos_embed[-Hp * Wp:]
     if cls_token is not None:
         row = cls_token if pos_embed is None else cls_token + pos_embed[0]
         y = torch.cat((row.expand(N, 1, D), y), dim=1)
@@ -1004,6 +1025,83 @@ def _image_yuv420_patch_embed(frames, wk, bias_f, patch, pos_embed,
     return _image_u8_patch_embed(
         yuv420_to_rgb_u8(frames, chroma, matrix), wk, bias_f, P, pos_embed,
         cls_token, out_dtype, 0)
+
+
+RESIZE_PATCH_EMBED_PATCHES = (16, 32)
+
+
+def image_u8_resize_patch_embed(images, size, wk, bias_f, patch, crop=None,
+                                pos_embed=None, cls_token=None,
+                                out_dtype=None):
+    """Fused ViT patch embedding of images of any size: contiguous uint8
+    ``[N,Hin,Win,3]`` images are resized to a virtual ``size=(Hr,Wr)`` image
+    and the window ``crop=(top,left,Hc,Wc)`` of it (``None``: all of it) goes
+    to tokens ``[N,T,D]``, in one kernel launch. ``size`` and ``crop`` mean
+    what they mean in :func:`image_u8_resize_to_float` (bilinear, no
+    antialiasing); ``Hc`` and ``Wc`` are positive multiples of ``patch``,
+    which is 16 or 32. ``(wk, bias_f)`` are those of :func:`patch_embed_fold`,
+    unchanged; ``pos_embed``, ``cls_token``, ``out_dtype`` and ``T`` are those
+    of :func:`image_u8_patch_embed` with ``H, W := Hc, Wc``.
+
+    The operand of output pixel ``(oy, ox)`` of the window, channel ``c``, is
+    the blend ``v = t + wy*(b - t)`` of :func:`image_u8_resize_to_float`
+    before its normalization, from the same fp32 operations. It reaches the
+    bf16 matrix cores as two pieces::
+
+        hi = bf16_rne(v)      lo = bf16_rne(v - hi)      a = hi + lo
+        out[n, t0 + hp*Wp + wp, d] = out_dtype(
+            sum_k a_k * wk[d, k] + bias_f[d] + pos_embed[t0 + hp*Wp + wp, d])
+
+    ``v - hi`` is exact in fp32, so ``|v - a| <= 2**-16 * |v|``. Accumulation
+    is fp32: per 32 values of ``k`` the ``hi`` products, then the ``lo``
+    products, ascending ``k``, one accumulator; class-token rows and the
+    epilogue are those of :func:`image_u8_patch_embed`. Deterministic. With
+    ``size == (Hin,Win)`` and ``crop=None`` the weights are exactly 0, ``lo``
+    is 0 and the result is bit-identical to :func:`image_u8_patch_embed`; a
+    cropped call equals the same tokens of any call whose window holds the
+    same pixels of the resized image, since the taps depend on the position
+    in the resized image alone.
+
+    Device tensors run the gfx950 kernel, which resamples while it fills its
+    tile: neither the resized image nor an fp32 tensor exists in device
+    memory, no eager fallback. CPU tensors run an eager expression: the
+    blends of :func:`image_u8_resize_to_float`, the split, an fp32 matmul and
+    the same epilogue, the same semantics without bit-identity to the device.
+    All sides must be in 1..16384. ``N == 0`` returns an empty tensor.
+    Invalid arguments raise ``ValueError`` on both paths."""
+    return _image_u8_resize_patch_embed(images, size, wk, bias_f, patch, crop,
+                                        pos_embed, cls_token, out_dtype, 0)
+
+
+def _image_u8_resize_patch_embed(images, size, wk, bias_f, patch, crop,
+                                 pos_embed, cls_token, out_dtype, tile):
+    """:func:`image_u8_resize_patch_embed` with the kernel's tile forced, as
+    :func:`_image_u8_patch_embed`."""
+    name = "image_u8_resize_patch_embed"
+    if isinstance(patch, bool) or patch not in RESIZE_PATCH_EMBED_PATCHES:
+        raise ValueError(
+            f"{name}: patch must be one of {RESIZE_PATCH_EMBED_PATCHES}, got "
+            f"{patch!r}")
+    P = int(patch)
+    N, Hin, Win = _patch_embed_images(name, images)
+    Hr, Wr, top, left, Hc, Wc, rh, rw = _resize_window(
+        name, Hin, Win, size, crop)
+    out_dtype, T, D = _patch_embed_operands(
+        name, images, Hc, Wc, P, wk, bias_f, pos_embed, cls_token, out_dtype)
+    if N == 0:
+        return torch.empty((0, T, D), dtype=out_dtype, device=images.device)
+    if images.is_cuda:
+        return require_native().u8_resize_patch_embed(
+            images, rh, rw, top, left, Hc, Wc, wk, bias_f, P, pos_embed,
+            cls_token, out_dtype, int(tile))
+    # mean 0, std 1, pixel_scale 1: v * 1 + (-0) is v
+    v = image_u8_resize_to_float(
+        images, (Hr, Wr), (0.0,) * 3, (1.0,) * 3, crop=(top, left, Hc, Wc),
+        layout="nhwc", pixel_scale=1.0)
+    hi = v.bfloat16().float()
+    lo = (v - hi).bfloat16().float()
+    return _patch_embed_eager(hi + lo, wk, bias_f, P, pos_embed, cls_token,
+                              out_dtype)
 
 
 def masked_mean_pool(hidden, mask=None, normalize=False):

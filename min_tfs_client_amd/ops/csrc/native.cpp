@@ -80,6 +80,13 @@ at::Tensor yuv420_patch_embed(const at::Tensor& frames, const at::Tensor& wk,
                               const c10::optional<at::Tensor>& cls,
                               at::ScalarType out_dtype, int64_t tile,
                               bool i420, std::vector<int64_t> coef);
+at::Tensor u8_resize_patch_embed(const at::Tensor& images, double rh,
+                                 double rw, int64_t top, int64_t left,
+                                 int64_t Hc, int64_t Wc, const at::Tensor& wk,
+                                 const at::Tensor& bias, int64_t patch,
+                                 const c10::optional<at::Tensor>& pos,
+                                 const c10::optional<at::Tensor>& cls,
+                                 at::ScalarType out_dtype, int64_t tile);
 at::Tensor dequantize_q8(const at::Tensor& in, double scale, double zp);
 void copy_device_to_host_ptr(const at::Tensor& src, void* dst, size_t n,
                              int mode);
@@ -723,6 +730,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("pos"), py::arg("cls"),
         py::arg("out_dtype"), py::arg("tile"), py::arg("i420"),
         py::arg("coef"));
+  m.def("u8_resize_patch_embed", &mi355x::u8_resize_patch_embed,
+        py::arg("images"), py::arg("rh"), py::arg("rw"), py::arg("top"),
+        py::arg("left"), py::arg("crop_h"), py::arg("crop_w"), py::arg("wk"),
+        py::arg("bias"), py::arg("patch"), py::arg("pos"), py::arg("cls"),
+        py::arg("out_dtype"), py::arg("tile") = 0);
   m.def("quantize_q8", &mi355x::quantize_q8, py::arg("input"),
         py::arg("scale"), py::arg("zero_point") = 0.0);
   m.def("dequantize_q8", &mi355x::dequantize_q8, py::arg("input"),

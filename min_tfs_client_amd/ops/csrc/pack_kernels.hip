@@ -46,6 +46,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "resize_tap.h"
 #include "staging.h"
 #include "yuv420_convert.h"
 
@@ -577,18 +578,6 @@ struct U8ResizeParams {
   int tiles_x, tiles_y;
   int span_stride;   // LDS bytes per source-row span (multiple of 16), 0: direct
 };
-
-// Source index and weight of one output coordinate.
-__device__ __forceinline__ void resize_tap(int o, int offset, float ratio,
-                                           int n_in, int& i0, int& i1,
-                                           float& w) {
-  const float s = fmaxf(
-      __fsub_rn(__fmul_rn(__fadd_rn(float(o + offset), 0.5f), ratio), 0.5f),
-      0.f);
-  i0 = min(int(floorf(s)), n_in - 1);
-  i1 = min(i0 + 1, n_in - 1);
-  w = __fsub_rn(s, float(i0));
-}
 
 // Store one lane's run: the first min(kResizePx, Wc - ox0) columns of vout
 // (NCHW: [c][k], NHWC: [k][c]) to `dst`, the run's first output element.

@@ -32,8 +32,10 @@
 // MI355X (ViT-B/16, bf16 out): 8 images (78 large tiles) 19 us small against
 // 39 us large; 32 images (294 large tiles) 67 us small against 49 us large.
 //
-// One kernel body, patch_embed_kernel, and two A loaders (a template
-// parameter: PeRgbLoader, PeYuvLoader). The loader owns the A side of a K
+// One kernel body, patch_embed_kernel, and three A loaders (a template
+// parameter: PeRgbLoader, PeYuvLoader, PeResizeLoader: images of any size,
+// resized and cropped on the way in, see the end of this header; its large
+// tile is 64 x 128). The loader owns the A side of a K
 // step: how many bytes of K a step is (BK), the LDS row stride (STRIDE), the
 // per-row offsets, the global -> register prefetch and the register -> LDS
 // store. The MFMA loop, the B fragments, the epilogue and the class-token
@@ -118,6 +120,61 @@
 //    images 20 us small against 41 us large; 32 images 65 us small against
 //    49 us large), and the fused op takes 0.93-1.10 of the RGB kernel's time
 //    on converted frames (profiles/README.md).
+//
+// Resampling loader (PeResizeLoader, P = 16 and 32): images of any size,
+// [N,Hin,Win,3]; the K values of a token are the pixels of its patch in the
+// crop window of the bilinearly resized image, which never exists in memory.
+// A resized pixel is the fp32 blend v of the resize ingest (resize_tap.h and
+// the unfused t, b, v chain of pack_kernels.hip), not a bf16 number, so A is
+// two bf16 pieces, hi = bf16_rne(v) and lo = bf16_rne(v - hi) (v - hi is
+// exact, |v - (hi + lo)| <= 2^-16 |v|), and the loop issues the hi MFMA, then
+// the lo MFMA of every 32-wide slab into the one accumulator (PIECES = 2;
+// `frag` hands the loop a piece's fragment, the byte loaders widen there).
+// At the identity size the weights are 0, lo is 0 and the result is the RGB
+// kernel's, bit for bit.
+//  * A step is 32 pixels = 96 K values = 3 slabs per tile row, as for YUV
+//    (P = 16: patch rows 2s, 2s+1; P = 32: patch row s); K = Kp, no tail.
+//    The 32 * BM pixels are 256 units, one per thread: 8 (BM = 64) or 4
+//    (BM = 32) consecutive output columns of one output row. The tile rows'
+//    table holds token, image, the image's byte offset (int64) and the
+//    patch's first pixel in the resized image (row, column; top / left
+//    added: the taps depend on that sum alone).
+//  * Gathers are issued a step ahead, before the MFMAs, like the other
+//    loaders' loads: y0, y1, wy once per unit, x0 per pixel, then ONE 8-byte
+//    load per pixel and source row at the byte of pixel x0 (any alignment):
+//    x1 is x0 or x0 + 1, so both taps are in its first 6 bytes. resize_tap
+//    clamps every index into the image, and a load that would pass the end
+//    of the tensor starts at its last 8 bytes instead and is shifted down
+//    when it is used (a batch under 8 bytes is copied into 8), so no byte
+//    outside `images` is read for any ratio. Source spans are NOT staged in
+//    LDS: the gathers hit L1/L2, which the workgroups that share an A tile
+//    (D tiles run fastest) keep warm. Rows past M gather nothing and blend
+//    zero registers: +0 in both pieces.
+//  * The blend, the split (v_cvt_pk_bf16_f32) and the stores happen at store
+//    time. The fp32 chain is kept out of v_pk_*_f32 (pe_alone).
+//  * LDS tile: bf16, 4 bytes per K value. A row is 96 hi (192 B), 96 lo
+//    (192 B) and 16 B of padding: STRIDE = 400 B = 25 16-byte slots, odd. A
+//    lane's fragment of a piece is one 16-byte read (row lane % 16, K offset
+//    8 * (lane / 16)) already in MFMA layout; the 16 rows of a pass fall
+//    into 16 different slots of the 64 banks (25 r mod 16 is a permutation):
+//    conflict-free. Stores: 6 x 16 B per thread (BM = 64; a pass of 16 lanes
+//    is 4 rows x 4 units at slots 25 r + 3 q + const: 13 of 16 slots,
+//    two-way on three of them) or 6 x 8 B (BM = 32).
+//  * LDS budget: a 128-row double-buffered tile would be 100 KB. The large
+//    tile of this loader is kPeResizeLargeM x kPeLargeN = 64 x 128 (TM = 2,
+//    TN = 4), double-buffered, one barrier per step: 2 x 64 x 400 B + tables
+//    = 51.5 KB; the small tile 25.8 KB. The alternative, a single-buffered
+//    128-row tile with two barriers per step, was not built or measured.
+//  * gfx950 resource use (hipcc, ROCm 7.2): large tile 186 VGPRs + 32 AGPRs,
+//    small tile 80 + 4, no scratch; occupancy 2 / 5 waves per SIMD.
+//  * Measured on an MI355X (ViT-B/16, bf16 out, 480x640 -> 256 -> crop 224):
+//    8 images (150 large tiles) 40 us small against 52 us large; 32 images
+//    (588 large tiles) 130 us small against 112 us large (from 1080x1920:
+//    136 against 142, inside the spread). The crossover sits where the other
+//    loaders' does: kPeResizeLargeMinTiles = 256. One launch takes 0.20-0.81
+//    of the time of image_u8_resize_to_float + VisionTransformer.embed; the
+//    identity size costs 1.6-2.0 of the RGB kernel (the second MFMA piece,
+//    the bf16 tile and the blend). profiles/README.md.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
@@ -132,6 +189,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "resize_tap.h"
 #include "yuv420_convert.h"
 
 namespace mi355x {
@@ -141,6 +199,9 @@ constexpr int kPeThreads = 256;
 constexpr int kPeLargeM = 128, kPeLargeN = 128;
 constexpr int kPeSmallM = 32, kPeSmallN = 32;
 constexpr int64_t kPeLargeMinTiles = 256;
+// the resampling loader's large tile, see the header
+constexpr int kPeResizeLargeM = 64;
+constexpr int64_t kPeResizeLargeMinTiles = 256;
 
 typedef __bf16 pe_bf16x8 __attribute__((ext_vector_type(8)));
 typedef float pe_f32x4 __attribute__((ext_vector_type(4)));
@@ -160,6 +221,11 @@ struct PatchEmbedParams {
   int64_t frame;      // bytes of one frame, H*W*3/2
   int64_t vplane;     // I420: bytes from a U sample to its V, (H/2)*(W/2)
   Yuv420Coef k;
+  // resampling loader only: H x W above is the crop window of the resized
+  // image, img holds N source images of Hin x Win pixels
+  int Hin, Win, top, left;
+  float rh, rw;
+  int64_t src_last;   // offset of the last 8 bytes of img
 };
 
 struct PeOutF32 {
@@ -198,18 +264,28 @@ __device__ __forceinline__ pe_bf16x8 pe_widen8(uint2 v) {
   return u.f;
 }
 
+// one lane's A fragment of a byte tile: 8 bytes of row `row`, widened
+template <int STRIDE>
+__device__ __forceinline__ pe_bf16x8 pe_byte_frag(const uint8_t* buf, int row,
+                                                  int ks, int lgrp) {
+  return pe_widen8(*reinterpret_cast<const uint2*>(
+      &buf[row * STRIDE + ks * 32 + lgrp * 8]));
+}
+
 // ---------------------------------------------------------------------------
 // A loaders. A loader is one thread's share of the A side of the K loop: the
-// geometry of a step (BK bytes of K, STRIDE bytes per LDS tile row), the
-// offsets kept per tile row, `load(p, s)`: global memory -> registers for
-// step s, and `store(buf)`: registers -> the BM x BK byte tile at `buf`.
+// geometry of a step (BK values of K, STRIDE bytes per LDS tile row, PIECES
+// bf16 pieces whose sum is the operand), the offsets kept per tile row,
+// `load(p, s)`: global memory -> registers for step s, `store(buf)`:
+// registers -> the BM-row tile at `buf`, and `frag(buf, row, ks, lgrp,
+// piece)`: a lane's 8 K values of slab ks of that tile, in MFMA layout.
 // ---------------------------------------------------------------------------
 
 // RGB: the K bytes of a step are contiguous pixels of one or two patch rows.
 template <int P, int BM_>
 struct PeRgbLoader {
-  static constexpr int BM = BM_, BK = 64, STRIDE = 80;
-  static constexpr bool kChroma = false;
+  static constexpr int BM = BM_, BK = 64, STRIDE = 80, PIECES = 1;
+  static constexpr bool kAux = false;
   static constexpr int VEC = (P % 16 == 0) ? 16 : 2;   // bytes per A load
   static constexpr int ROWB = 3 * P;                   // bytes of a patch row
   static constexpr int UPR = BK / VEC;                 // load units per row
@@ -265,6 +341,10 @@ struct PeRgbLoader {
             a_reg[i];
     }
   }
+  static __device__ __forceinline__ pe_bf16x8 frag(const uint8_t* buf, int row,
+                                                  int ks, int lgrp, int) {
+    return pe_byte_frag<STRIDE>(buf, row, ks, lgrp);
+  }
 };
 
 // NB aligned bytes -> the low bytes of d[0..]
@@ -300,8 +380,8 @@ __device__ __forceinline__ int pe_byte(const uint32_t* w, int b) {
 template <int P, int BM_, bool I420>
 struct PeYuvLoader {
   static_assert(P == 16 || P == 32, "a 42-byte patch row fits no unit");
-  static constexpr int BM = BM_, BK = 96, STRIDE = 112;
-  static constexpr bool kChroma = true;
+  static constexpr int BM = BM_, BK = 96, STRIDE = 112, PIECES = 1;
+  static constexpr bool kAux = true;       // the chroma offsets
   static constexpr int UPR = kPeThreads / BM;          // units per tile row
   static_assert(UPR == 2 || UPR == 8, "one unit per thread");
   static constexpr int NR = (P == 16 && UPR == 2) ? 2 : 1;
@@ -418,22 +498,214 @@ struct PeYuvLoader {
       }
     }
   }
+  static __device__ __forceinline__ pe_bf16x8 frag(const uint8_t* buf, int row,
+                                                  int ks, int lgrp, int) {
+    return pe_byte_frag<STRIDE>(buf, row, ks, lgrp);
+  }
 };
 
+// two floats -> one register holding two bf16, round to nearest even (low
+// half: the first)
+__device__ __forceinline__ uint32_t pe_bf16_pair(float a, float b) {
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+  union { bf16x2 h; uint32_t u; } r;
+  r.h = __builtin_convertvector(f32x2{a, b}, bf16x2);
+  return r.u;
+}
+
+// One fp32 result on its own: the empty asm hides it from the compiler's
+// pairing of independent fp32 operations into v_pk_*_f32, so the blend below
+// is scalar v_sub / v_mul / v_add, one IEEE operation each (checked in the
+// ISA: no packed fp32 instruction in this file's kernels).
+__device__ __forceinline__ float pe_alone(float x) {
+  asm("" : "+v"(x));
+  return x;
+}
+
+// Bilinear resize + crop (resize_tap.h; the blend chain of resize_run in
+// pack_kernels.hip): the K values of a step are 32 pixels of the crop window
+// of the resized image, which never exists in memory. A step is 96 K values
+// per tile row, as for YUV: P = 16: patch rows 2s and 2s+1, P = 32: patch
+// row s. The 32 * BM pixels of a step are cut into 256 units, one per thread,
+// of PX consecutive output columns of one output row:
+//   BM = 64: 8 pixels     BM = 32: 4 pixels
+// load(): y0, y1, wy once per unit, x0 per pixel, and one 8-byte gather per
+// pixel and source row: x1 is x0 or x0 + 1, so both taps of a row lie in the
+// 6 bytes at pixel x0. The gather may start at any byte; it is moved back to
+// the last 8 bytes of the tensor where it would run past them and shifted
+// down again in store(). store(): x0, x1, wx again (cheaper than 8 more
+// registers), the unfused fp32 blend v, then hi = bf16_rne(v),
+// lo = bf16_rne(v - hi), both to the tile. A tile row is 96 hi values, then
+// 96 lo values, then padding: STRIDE = 400 bytes.
+// Where x1 == x0 (the right edge) the second tap in the 8 bytes is not the
+// pixel; the weight is then replaced by 0, and p00 + 0 * (g - p00) is p00
+// for any finite g, which is what p00 + wx * (p00 - p00) gives. A row past M
+// gathers nothing and keeps zero registers: their blend is +0 in both pieces
+// for any weights.
+template <int P, int BM_>
+struct PeResizeLoader {
+  static_assert(P == 16 || P == 32, "a 14-pixel patch row fits no unit");
+  static constexpr int BM = BM_, BK = 96, PIECES = 2;
+  static constexpr int PIECE = 2 * BK;                 // bytes of one piece
+  static constexpr int STRIDE = 2 * PIECE + 16;        // 25 16-byte slots
+  static constexpr bool kAux = true;                   // the pixel origins
+  static constexpr int UPR = kPeThreads / BM;          // units per tile row
+  static_assert(UPR == 4 || UPR == 8, "one unit per thread");
+  static constexpr int PX = 32 / UPR;                  // 8 or 4
+  static constexpr int LROWS = (P == 16) ? 2 : 1;      // output rows per step
+
+  int64_t img;           // byte offset of the unit's image; -1: row past M
+  int oy0, ox0;          // the unit's output pixel at step 0
+  int lds_off;
+  float wy;
+  int d[2];              // (offset of source row y0 / y1) - src_last, clamped
+  uint2 tap[2][PX];
+
+  // pix: byte offset of image n; aux: the output pixel (row << 32 | column)
+  // of the first pixel of patch (hp, wp) in the resized image
+  static __device__ __forceinline__ void offsets(
+      const PatchEmbedParams& p, int n, int hp, int wp, int64_t& pix,
+      int64_t& aux) {
+    pix = int64_t(n) * p.Hin * p.Win * 3;
+    aux = (int64_t(hp * P + p.top) << 32) | int64_t(wp * P + p.left);
+  }
+  __device__ __forceinline__ void init(const PatchEmbedParams&, int tid,
+                                       const int64_t* row_pix,
+                                       const int64_t* row_aux,
+                                       const int* row_tok) {
+    const int r = tid / UPR, q = tid % UPR;
+    const int kp = q * PX;                             // pixel of K in a step
+    const int j0 = (P == 16) ? kp / 16 : 0, px0 = (P == 16) ? kp % 16 : kp;
+    lds_off = r * STRIDE + kp * 6;
+    img = row_tok[r] >= 0 ? row_pix[r] : int64_t(-1);
+    oy0 = int(row_aux[r] >> 32) + j0;
+    ox0 = int(row_aux[r] & 0xffffffff) + px0;
+    wy = 0.f;
+    d[0] = d[1] = -(1 << 30);                          // no shift
+  }
+  __device__ __forceinline__ void load(const PatchEmbedParams& p, int s) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int i = 0; i < PX; ++i) tap[j][i] = uint2{0u, 0u};
+    if (img < 0) return;
+    int y[2];
+    resize_tap(oy0 + s * LROWS, 0, p.rh, p.Hin, y[0], y[1], wy);
+    int64_t row[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      row[j] = img + int64_t(y[j]) * p.Win * 3;
+      const int64_t over = row[j] - p.src_last;
+      d[j] = int(over > -(int64_t(1) << 30) ? over : -(int64_t(1) << 30));
+    }
+#pragma unroll
+    for (int i = 0; i < PX; ++i) {
+      int x0, x1;
+      float wx;
+      resize_tap(ox0 + i, 0, p.rw, p.Win, x0, x1, wx);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        // row + x0*3 + 3 <= bytes of img, src_last >= 0: inside the tensor
+        const int64_t a = row[j] + x0 * 3;
+        __builtin_memcpy(&tap[j][i],
+                         p.img + (a < p.src_last ? a : p.src_last), 8);
+      }
+    }
+  }
+  __device__ __forceinline__ void store(const PatchEmbedParams& p,
+                                        uint8_t* buf) const {
+    uint32_t hi[3 * PX / 2], lo[3 * PX / 2];
+    float v[3 * PX];
+#pragma unroll
+    for (int i = 0; i < PX; ++i) {
+      int x0, x1;
+      float wx;
+      resize_tap(ox0 + i, 0, p.rw, p.Win, x0, x1, wx);
+      wx = x1 == x0 ? 0.f : wx;
+      uint32_t w[2][2];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int sh = 8 * max(d[j] + x0 * 3, 0);      // 0 .. 40
+        const uint64_t t =
+            ((uint64_t(tap[j][i].y) << 32) | tap[j][i].x) >> sh;
+        w[j][0] = uint32_t(t);
+        w[j][1] = uint32_t(t >> 32);
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float p00 = float(pe_byte(w[0], c));
+        const float p01 = float(pe_byte(w[0], 3 + c));
+        const float p10 = float(pe_byte(w[1], c));
+        const float p11 = float(pe_byte(w[1], 3 + c));
+        const float t = pe_alone(__fadd_rn(p00, pe_alone(__fmul_rn(
+            wx, pe_alone(__fsub_rn(p01, p00))))));
+        const float b = pe_alone(__fadd_rn(p10, pe_alone(__fmul_rn(
+            wx, pe_alone(__fsub_rn(p11, p10))))));
+        v[3 * i + c] = pe_alone(__fadd_rn(t, pe_alone(__fmul_rn(
+            wy, pe_alone(__fsub_rn(b, t))))));
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 3 * PX / 2; ++k) {
+      const float a = v[2 * k], b = v[2 * k + 1];
+      hi[k] = pe_bf16_pair(a, b);
+      // v - hi is exact: hi keeps the leading 8 bits of v
+      lo[k] = pe_bf16_pair(
+          pe_alone(__fsub_rn(a, __uint_as_float(hi[k] << 16))),
+          pe_alone(__fsub_rn(b, __uint_as_float(hi[k] & 0xffff0000u))));
+    }
+    uint8_t* dst = buf + lds_off;
+    if constexpr (PX == 8) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        *reinterpret_cast<uint4*>(dst + 16 * q) =
+            uint4{hi[4 * q], hi[4 * q + 1], hi[4 * q + 2], hi[4 * q + 3]};
+        *reinterpret_cast<uint4*>(dst + PIECE + 16 * q) =
+            uint4{lo[4 * q], lo[4 * q + 1], lo[4 * q + 2], lo[4 * q + 3]};
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        *reinterpret_cast<uint2*>(dst + 8 * q) =
+            uint2{hi[2 * q], hi[2 * q + 1]};
+        *reinterpret_cast<uint2*>(dst + PIECE + 8 * q) =
+            uint2{lo[2 * q], lo[2 * q + 1]};
+      }
+    }
+  }
+  // 8 K-contiguous bf16 of one piece: one 16-byte read, already MFMA layout
+  static __device__ __forceinline__ pe_bf16x8 frag(const uint8_t* buf, int row,
+                                                  int ks, int lgrp,
+                                                  int piece) {
+    return *reinterpret_cast<const pe_bf16x8*>(
+        &buf[row * STRIDE + piece * PIECE + ks * 64 + lgrp * 16]);
+  }
+};
+
+// A source: its loader for a tile of BM rows, and the rows of its large tile
 template <int P>
 struct PeRgb {
+  static constexpr int kLargeM = kPeLargeM;
   template <int BM> using Loader = PeRgbLoader<P, BM>;
 };
 template <int P, bool I420>
 struct PeYuv {
+  static constexpr int kLargeM = kPeLargeM;
   template <int BM> using Loader = PeYuvLoader<P, BM, I420>;
 };
+template <int P>
+struct PeResize {
+  static constexpr int kLargeM = kPeResizeLargeM;
+  template <int BM> using Loader = PeResizeLoader<P, BM>;
+};
 
-// the chroma offsets of the tile rows: LDS only in kernels whose loader asks
+// a second int64 per tile row (chroma offset, pixel origin): LDS only in
+// kernels whose loader asks
 template <int BM>
-__device__ __forceinline__ int64_t* pe_chroma_table() {
-  __shared__ int64_t row_chr[BM];
-  return row_chr;
+__device__ __forceinline__ int64_t* pe_aux_table() {
+  __shared__ int64_t row_aux[BM];
+  return row_aux;
 }
 
 template <typename LD, int TN, typename OUT>
@@ -447,8 +719,8 @@ patch_embed_kernel(const PatchEmbedParams p) {
   __shared__ int64_t row_pix[BM];   // byte offset of the patch's first pixel
   __shared__ int row_tok[BM];       // token index inside the image, -1: past M
   __shared__ int row_img[BM];
-  int64_t* row_chr = nullptr;       // offset of the patch's first chroma
-  if constexpr (LD::kChroma) row_chr = pe_chroma_table<BM>();
+  int64_t* row_aux = nullptr;       // first chroma offset / pixel origin
+  if constexpr (LD::kAux) row_aux = pe_aux_table<BM>();
 
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int wm = wave >> 1, wn = wave & 1;
@@ -460,22 +732,22 @@ patch_embed_kernel(const PatchEmbedParams p) {
   if (tid < BM) {
     const int m = m0 + tid;
     int tok = -1, n = 0;
-    int64_t pix = 0, chr = 0;
+    int64_t pix = 0, aux = 0;
     if (m < p.M) {
       n = m / p.HW;
       tok = m - n * p.HW;
       const int hp = tok / p.Wp, wp = tok - hp * p.Wp;
-      LD::offsets(p, n, hp, wp, pix, chr);
+      LD::offsets(p, n, hp, wp, pix, aux);
     }
     row_pix[tid] = pix;
-    if constexpr (LD::kChroma) row_chr[tid] = chr;
+    if constexpr (LD::kAux) row_aux[tid] = aux;
     row_tok[tid] = tok;
     row_img[tid] = n;
   }
   __syncthreads();
 
   LD ld;
-  ld.init(p, tid, row_pix, row_chr, row_tok);
+  ld.init(p, tid, row_pix, row_aux, row_tok);
 
   // B rows of this lane; a block past D reads row D-1 and is never stored
   const uint16_t* b_row[TN];
@@ -523,21 +795,23 @@ patch_embed_kernel(const PatchEmbedParams p) {
     }
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      pe_bf16x8 a[TM];
+      // the pieces of a slab in order (hi, then lo) into the one accumulator
 #pragma unroll
-      for (int tm = 0; tm < TM; ++tm) {
-        const int r = (wm * TM + tm) * 16 + lrow;
-        a[tm] = pe_widen8(*reinterpret_cast<const uint2*>(
-            &a_lds[buf][r * LD::STRIDE + ks * 32 + lgrp * 8]));
-      }
-#pragma unroll
-      for (int tn = 0; tn < TN; ++tn) {
-        union { uint4 u; pe_bf16x8 f; } b;
-        b.u = b_cur[ks][tn];
+      for (int piece = 0; piece < LD::PIECES; ++piece) {
+        pe_bf16x8 a[TM];
 #pragma unroll
         for (int tm = 0; tm < TM; ++tm)
-          acc[tm][tn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              a[tm], b.f, acc[tm][tn], 0, 0, 0);
+          a[tm] = LD::frag(a_lds[buf], (wm * TM + tm) * 16 + lrow, ks, lgrp,
+                           piece);
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn) {
+          union { uint4 u; pe_bf16x8 f; } b;
+          b.u = b_cur[ks][tn];
+#pragma unroll
+          for (int tm = 0; tm < TM; ++tm)
+            acc[tm][tn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                a[tm], b.f, acc[tm][tn], 0, 0, 0);
+        }
       }
     }
   }
@@ -596,30 +870,38 @@ void launch_patch_embed_out(at::ScalarType out_dtype,
     launch_patch_embed<LD, TN, PeOutF16>(p, tiles, stream);
 }
 
-// SRC: PeRgb<P> or PeYuv<P, I420>
+// SRC: PeRgb<P>, PeYuv<P, I420> or PeResize<P>
 template <typename SRC>
 void launch_patch_embed_tile(bool large, at::ScalarType out_dtype,
                              const PatchEmbedParams& p, int64_t tiles,
                              hipStream_t stream) {
   if (large)
-    launch_patch_embed_out<typename SRC::template Loader<kPeLargeM>,
+    launch_patch_embed_out<typename SRC::template Loader<SRC::kLargeM>,
                            kPeLargeN / 32>(out_dtype, p, tiles, stream);
   else
     launch_patch_embed_out<typename SRC::template Loader<kPeSmallM>,
                            kPeSmallN / 32>(out_dtype, p, tiles, stream);
 }
 
-enum class PeSource { kRgb, kNv12, kI420 };
+enum class PeSource { kRgb, kNv12, kI420, kResize };
 
-// The part of the two entry points below that does not depend on the pixel
-// format: `in` holds N images of H x W pixels and was checked by the caller.
+// kResize only: the source geometry, checked by the caller
+struct PeResizeArgs {
+  int64_t Hin = 0, Win = 0, top = 0, left = 0;
+  float rh = 0.f, rw = 0.f;
+};
+
+// The part of the entry points below that does not depend on the pixel
+// format: `in` holds N images that give H x W pixels each (kResize: H x W is
+// the crop window, `rz` the source side) and was checked by the caller.
 at::Tensor patch_embed_run(const char* who, const at::Tensor& in,
                            PeSource src, const Yuv420Coef& coef, int64_t N,
                            int64_t H, int64_t W, const at::Tensor& wk,
                            const at::Tensor& bias, int64_t patch,
                            const c10::optional<at::Tensor>& pos,
                            const c10::optional<at::Tensor>& cls,
-                           at::ScalarType out_dtype, int64_t tile) {
+                           at::ScalarType out_dtype, int64_t tile,
+                           const PeResizeArgs& rz = PeResizeArgs{}) {
   TORCH_CHECK_VALUE(out_dtype == at::kFloat || out_dtype == at::kBFloat16 ||
                     out_dtype == at::kHalf,
                     who, ": out_dtype must be f32, bf16 or f16");
@@ -655,9 +937,12 @@ at::Tensor patch_embed_run(const char* who, const at::Tensor& in,
                     D <= (1 << 20) && H <= (1 << 20) && W <= (1 << 20), who,
                     ": too many tokens or too large a side");
   // 16-byte loads of pixels (P = 16, 32) and of weight fragments; the YUV
-  // units' narrower loads are aligned to their width when the frames are
+  // units' narrower loads are aligned to their width when the frames are;
+  // the resampling loader gathers at any byte
+  const bool resize = src == PeSource::kResize;
   TORCH_CHECK_VALUE(
-      reinterpret_cast<uintptr_t>(in.const_data_ptr()) % 16 == 0 &&
+      (resize ||
+       reinterpret_cast<uintptr_t>(in.const_data_ptr()) % 16 == 0) &&
       reinterpret_cast<uintptr_t>(wk.const_data_ptr()) % 16 == 0, who,
       ": images and wk must be 16-byte aligned");
 
@@ -667,10 +952,12 @@ at::Tensor patch_embed_run(const char* who, const at::Tensor& in,
   auto tiles_of = [&](int64_t bm, int64_t bn) {
     return ((M + bm - 1) / bm) * ((D + bn - 1) / bn);
   };
+  const int64_t large_m = resize ? kPeResizeLargeM : kPeLargeM;
   const bool large = tile == 2 ||
-      (tile == 0 && tiles_of(kPeLargeM, kPeLargeN) >= kPeLargeMinTiles);
+      (tile == 0 && tiles_of(large_m, kPeLargeN) >=
+           (resize ? kPeResizeLargeMinTiles : kPeLargeMinTiles));
   const int64_t bn = large ? kPeLargeN : kPeSmallN;
-  const int64_t tiles = large ? tiles_of(kPeLargeM, kPeLargeN)
+  const int64_t tiles = large ? tiles_of(large_m, kPeLargeN)
                               : tiles_of(kPeSmallM, kPeSmallN);
   TORCH_CHECK_VALUE(tiles <= std::numeric_limits<int32_t>::max(), who,
                     ": too many tiles");
@@ -691,10 +978,21 @@ at::Tensor patch_embed_run(const char* who, const at::Tensor& in,
   p.frame = H * W * 3 / 2;
   p.vplane = (H / 2) * (W / 2);
   p.k = coef;
+  p.Hin = int(rz.Hin); p.Win = int(rz.Win);
+  p.top = int(rz.top); p.left = int(rz.left);
+  p.rh = rz.rh; p.rw = rz.rw;
+  p.src_last = in.numel() - 8;            // kResize: the caller saw to >= 0
 
   hipStream_t stream = at::hip::getCurrentHIPStream().stream();
   const bool p16 = patch == 16;
-  if (src == PeSource::kNv12) {
+  if (resize) {
+    if (p16)
+      launch_patch_embed_tile<PeResize<16>>(large, out_dtype, p, tiles,
+                                            stream);
+    else
+      launch_patch_embed_tile<PeResize<32>>(large, out_dtype, p, tiles,
+                                            stream);
+  } else if (src == PeSource::kNv12) {
     if (p16)
       launch_patch_embed_tile<PeYuv<16, false>>(large, out_dtype, p, tiles,
                                                 stream);
@@ -779,6 +1077,53 @@ at::Tensor yuv420_patch_embed(const at::Tensor& frames, const at::Tensor& wk,
   return patch_embed_run(who, frames, i420 ? PeSource::kI420 : PeSource::kNv12,
                          k, frames.size(0), H, W, wk, bias, patch, pos, cls,
                          out_dtype, tile);
+}
+
+// The same from images of any size: ``images`` is uint8 [N,Hin,Win,3]; the
+// tokens are those of the Hc x Wc window at (top, left) of the bilinear
+// resize whose ratios ``rh`` / ``rw`` are float(Hin/Hr) / float(Win/Wr),
+// rounded by the caller exactly as for u8_nhwc_resize_normalize
+// (ops.image_u8_resize_patch_embed, which also validates the window against
+// the resized size). The operand is the fp32 blend as two bf16 pieces, see
+// the header. Patches are 16 and 32.
+at::Tensor u8_resize_patch_embed(const at::Tensor& images, double rh,
+                                 double rw, int64_t top, int64_t left,
+                                 int64_t Hc, int64_t Wc, const at::Tensor& wk,
+                                 const at::Tensor& bias, int64_t patch,
+                                 const c10::optional<at::Tensor>& pos,
+                                 const c10::optional<at::Tensor>& cls,
+                                 at::ScalarType out_dtype, int64_t tile) {
+  const char* who = "u8_resize_patch_embed";
+  constexpr int64_t kMaxSide = 16384;
+  TORCH_CHECK_VALUE(images.is_cuda() && images.dim() == 4 &&
+                    images.is_contiguous() &&
+                    images.scalar_type() == at::kByte && images.size(3) == 3,
+                    who, " expects a contiguous uint8 device tensor "
+                    "[N,Hin,Win,3]");
+  TORCH_CHECK_VALUE(patch == 16 || patch == 32, who,
+                    ": patch must be 16 or 32, got ", patch);
+  const int64_t N = images.size(0), Hin = images.size(1),
+                Win = images.size(2);
+  TORCH_CHECK_VALUE(Hin >= 1 && Hin <= kMaxSide && Win >= 1 &&
+                    Win <= kMaxSide, who,
+                    ": input sides must be in 1..16384");
+  TORCH_CHECK_VALUE(Hc >= 1 && Wc >= 1 && top >= 0 && left >= 0 &&
+                    top + Hc <= kMaxSide && left + Wc <= kMaxSide, who,
+                    ": bad crop window");
+  TORCH_CHECK_VALUE(rh > 0.0 && rw > 0.0 && rh <= double(kMaxSide) &&
+                    rw <= double(kMaxSide), who,
+                    ": ratios must be in (0, 16384]");
+  // the loader gathers 8 bytes at a time: a smaller batch gets a tail
+  at::Tensor src = images;
+  if (N > 0 && images.numel() < 8) {
+    src = at::zeros({8}, images.options());
+    src.narrow(0, 0, images.numel()).copy_(images.view({-1}));
+  }
+  PeResizeArgs rz;
+  rz.Hin = Hin; rz.Win = Win; rz.top = top; rz.left = left;
+  rz.rh = float(rh); rz.rw = float(rw);
+  return patch_embed_run(who, src, PeSource::kResize, Yuv420Coef{}, N, Hc, Wc,
+                         wk, bias, patch, pos, cls, out_dtype, tile, rz);
 }
 
 }  // namespace mi355x

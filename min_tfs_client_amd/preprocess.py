@@ -24,7 +24,9 @@ antialiased filter, in two launches.
 straight to encoder tokens, normalization, patch projection, class token and
 position embedding in one matrix-core kernel (``ops.image_u8_patch_embed``);
 ``Yuv420PatchEmbedPreprocess`` feeds the same kernel NV12 or I420 frames,
-converted while the tile is filled (``ops.image_yuv420_patch_embed``).
+converted while the tile is filled (``ops.image_yuv420_patch_embed``), and
+``ResizePatchEmbedPreprocess`` images of any size, resized and centre-cropped
+while the tile is filled (``ops.image_u8_resize_patch_embed``).
 """
 from __future__ import annotations
 
@@ -61,6 +63,31 @@ def _int_or_pair(value, what):
             raise ValueError(f"{what} must be an int or (H, W), got {value!r}")
         return (_positive_int(value[0], what), _positive_int(value[1], what))
     return _positive_int(value, what)
+
+
+def _resized_size(resize, height, width):
+    """The ``resize`` rule of :class:`ImagePreprocess`: ``(Hr, Wr)`` for an
+    input of ``height x width``."""
+    if resize is None:
+        return height, width
+    if isinstance(resize, tuple):
+        return resize
+    if height <= width:
+        return resize, resize * width // height
+    return resize * height // width, resize
+
+
+def _crop_window(center_crop, resized_height, resized_width):
+    """The ``center_crop`` rule of :class:`ImagePreprocess`: ``(top, left,
+    Hc, Wc)`` inside the resized image, or ``None``."""
+    if center_crop is None:
+        return None
+    hc, wc = center_crop
+    if hc > resized_height or wc > resized_width:
+        raise ValueError(
+            f"center_crop {hc}x{wc} is larger than the resized image "
+            f"{resized_height}x{resized_width}")
+    return ((resized_height - hc) // 2, (resized_width - wc) // 2, hc, wc)
 
 
 def _as_tensor(x):
@@ -128,26 +155,11 @@ class ImagePreprocess:
 
     def resized_size(self, height: int, width: int):
         """``(Hr, Wr)`` of the resized image for an input of this size."""
-        if self.resize is None:
-            return height, width
-        if isinstance(self.resize, tuple):
-            return self.resize
-        s = self.resize
-        if height <= width:
-            return s, s * width // height
-        return s * height // width, s
+        return _resized_size(self.resize, height, width)
 
     def crop_window(self, resized_height: int, resized_width: int):
         """``(top, left, Hc, Wc)`` inside the resized image, or ``None``."""
-        if self.center_crop is None:
-            return None
-        hc, wc = self.center_crop
-        if hc > resized_height or wc > resized_width:
-            raise ValueError(
-                f"center_crop {hc}x{wc} is larger than the resized image "
-                f"{resized_height}x{resized_width}")
-        return ((resized_height - hc) // 2, (resized_width - wc) // 2,
-                hc, wc)
+        return _crop_window(self.center_crop, resized_height, resized_width)
 
     def __call__(self, x):
         x = _as_tensor(x)
@@ -460,6 +472,63 @@ class Yuv420PatchEmbedPreprocess(PatchEmbedPreprocess):
         return ops.image_yuv420_patch_embed(
             x, wk, bias_f, self.patch, pos_embed=pos, cls_token=cls,
             out_dtype=self.out_dtype, chroma=self.chroma, matrix=self.matrix)
+
+
+class ResizePatchEmbedPreprocess(PatchEmbedPreprocess):
+    """uint8 ``[N,H,W,3]`` pixels of any size -> ViT tokens ``[N,T,D]``: the
+    bilinear resize and the centre crop happen inside the patch-embedding
+    kernel (``ops.image_u8_resize_patch_embed``), which resamples while it
+    fills its tile.
+
+    ``resize`` and ``center_crop`` follow the rules of
+    :class:`ImagePreprocess` (an int ``resize`` sets the shorter side and
+    keeps the aspect ratio); at least one is needed, and the window they give
+    must be a multiple of the patch, which is 16 or 32. Every image of one
+    request has the same size; requests may differ. Everything else, the lazy
+    refold included, is :class:`PatchEmbedPreprocess`. The resized pixel is
+    an fp32 blend and reaches the matrix cores as two bf16 pieces, within
+    ``2**-16`` of its value."""
+
+    def __init__(self, weight, bias, mean, std, pos_embed=None,
+                 cls_token=None, out_dtype=None,
+                 pixel_scale: float = 1.0 / 255.0, device=None,
+                 resize=None, center_crop=None):
+        super().__init__(weight, bias, mean, std, pos_embed=pos_embed,
+                         cls_token=cls_token, out_dtype=out_dtype,
+                         pixel_scale=pixel_scale, device=device)
+        if self.patch not in ops.RESIZE_PATCH_EMBED_PATCHES:
+            raise ValueError(
+                f"patch must be one of {ops.RESIZE_PATCH_EMBED_PATCHES} for "
+                f"resized input, got {self.patch}")
+        self.resize = _int_or_pair(resize, "resize")
+        crop = _int_or_pair(center_crop, "center_crop")
+        self.center_crop = (crop, crop) if isinstance(crop, int) else crop
+        if self.resize is None and self.center_crop is None:
+            raise ValueError(
+                "ResizePatchEmbedPreprocess needs resize or center_crop; "
+                "PatchEmbedPreprocess serves images at their own size")
+
+    def resized_size(self, height: int, width: int):
+        """``(Hr, Wr)`` of the resized image for an input of this size."""
+        return _resized_size(self.resize, height, width)
+
+    def crop_window(self, resized_height: int, resized_width: int):
+        """``(top, left, Hc, Wc)`` inside the resized image, or ``None``."""
+        return _crop_window(self.center_crop, resized_height, resized_width)
+
+    def __call__(self, x):
+        x = _as_tensor(x)
+        if self.device is not None and x.dtype == torch.uint8:
+            x = x.to(self.device)
+        if x.dim() != 4 or x.shape[1] < 1 or x.shape[2] < 1:
+            raise ValueError(
+                "image input must be [N,H,W,3] with non-empty images, got "
+                f"shape {list(x.shape)}")
+        size = self.resized_size(int(x.shape[1]), int(x.shape[2]))
+        wk, bias_f, pos, cls = self.folded()
+        return ops.image_u8_resize_patch_embed(
+            x, size, wk, bias_f, self.patch, crop=self.crop_window(*size),
+            pos_embed=pos, cls_token=cls, out_dtype=self.out_dtype)
 
 
 def pack_ragged_images(images):

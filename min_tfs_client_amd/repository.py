@@ -35,8 +35,10 @@ On-disk version-directory formats understood by the default loader:
                                "normalize_embedding" (bert_base); vit_b16
                                takes "input_format" ("float_nchw",
                                "uint8_nhwc": raw pixels into the fused
-                               patch-embedding kernel, or "nv12" / "i420":
-                               YUV 4:2:0 frames into the same kernel),
+                               patch-embedding kernel, "uint8_nhwc_resize":
+                               pixels of any size, resized and cropped in
+                               the same kernel, or "nv12" / "i420": YUV
+                               4:2:0 frames into the same kernel),
                                "yuv_matrix" (with the YUV modes),
                                "output_format" ("logits" or "topk") and
                                "top_k"

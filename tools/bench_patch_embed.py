@@ -4,6 +4,7 @@ composed chain a user would run without it, one GPU.
 
     python tools/bench_patch_embed.py          # JSON lines
     python tools/bench_patch_embed.py --yuv    # NV12 / I420 input, see below
+    python tools/bench_patch_embed.py --resize # resize + crop input, see below
 
 The parent process never touches the GPU; the timings run in one fresh child
 process under a time limit, and the tool exits non-zero if it fails.
@@ -34,6 +35,14 @@ output, the same shapes and batches, per tile (rule, small, large):
 
 with the ratios (a)/(b) and (c)/(a), and ``identical``: whether (a) and (c)
 gave the same bits.
+
+``--resize``: ``ops.image_u8_resize_patch_embed`` (shorter side to 256,
+centre crop 224) from 480x640 and 1080x1920 images, batch 1, 8 and 32, bf16
+and fp32, per tile, against ``two_step_ms``, what a user runs without it:
+``ops.image_u8_resize_to_float`` then ``VisionTransformer.embed``. The
+224x224 rows are the identity-size call against ``image_u8_patch_embed``
+(``rgb_*_ms``): the cost of the second MFMA piece and the bf16 tile.
+``max_over_min_round`` is the largest spread of one timing over the rounds.
 """
 import json
 import os
@@ -174,12 +183,84 @@ def run_yuv_cases():
             print(json.dumps(row), flush=True)
 
 
+def run_resize_cases():
+    import torch
+
+    from min_tfs_client_amd import ops
+    from min_tfs_client_amd.models import vit_b16
+    from min_tfs_client_amd.preprocess import IMAGENET_MEAN, IMAGENET_STD
+
+    dev, P, S = "cuda:0", 16, 224
+    torch.manual_seed(0)
+    model = vit_b16().to(dev).eval()
+    wk, bias_f = ops.patch_embed_fold(
+        model.patch_embed.weight, model.patch_embed.bias, IMAGENET_MEAN,
+        IMAGENET_STD)
+    pos = model.pos_embed.detach().float()[0].contiguous()
+    cls = model.cls_token.detach().float().reshape(-1)
+    g = torch.Generator().manual_seed(0)
+    for dtype_name in DTYPES:
+        dtype = getattr(torch, dtype_name)
+        m = model.to(dtype)
+        # the identity size is the cost of the second piece and the bf16 tile
+        for hw in ((480, 640), (1080, 1920), (S, S)):
+            Hr, Wr = (256, 256 * hw[1] // hw[0]) if hw[0] != S else hw
+            crop = ((Hr - S) // 2, (Wr - S) // 2, S, S)
+            for N in (1, 8, 32):
+                x = torch.randint(0, 256, (N, *hw, 3), dtype=torch.uint8,
+                                  generator=g).to(dev)
+
+                def fused(tile=0):
+                    return ops._image_u8_resize_patch_embed(
+                        x, (Hr, Wr), wk, bias_f, P, crop, pos, cls, dtype,
+                        tile)
+
+                @torch.no_grad()
+                def two_step():
+                    return m.embed(ops.image_u8_resize_to_float(
+                        x, (Hr, Wr), IMAGENET_MEAN, IMAGENET_STD, crop=crop,
+                        out_dtype=dtype))
+
+                def rgb(tile=0):
+                    return ops._image_u8_patch_embed(
+                        x, wk, bias_f, P, pos, cls, dtype, tile)
+
+                other = two_step if hw[0] != S else rgb
+                diff = (fused().float() - other().float()).abs().max().item()
+                fns = [lambda t=t: fused(t) for t in TILES.values()] + [other]
+                if hw[0] == S:
+                    fns += [lambda: rgb(1), lambda: rgb(2)]
+                rounds = [[time_kernel(f, 100, 10) for f in fns]
+                          for _ in range(5)]
+                ms = [sorted(r[i] for r in rounds)[2]
+                      for i in range(len(fns))]
+                spread = max(max(r[i] for r in rounds) /
+                             min(r[i] for r in rounds)
+                             for i in range(len(fns)))
+                row = {"case": f"{N}x{hw[0]}x{hw[1]}_{dtype_name}"}
+                for name, t in zip(TILES, ms):
+                    row[f"fused_{name}_ms"] = round(t, 4)
+                if hw[0] != S:
+                    row["two_step_ms"] = round(ms[3], 4)
+                    row["two_step_over_fused"] = round(ms[3] / ms[0], 2)
+                else:
+                    for name, t in zip(TILES, ms[3:]):
+                        row[f"rgb_{name}_ms"] = round(t, 4)
+                    row["fused_over_rgb"] = round(ms[0] / ms[3], 2)
+                row.update({"max_over_min_round": round(spread, 2),
+                            "max_abs_diff": diff})
+                print(json.dumps(row), flush=True)
+
+
 def main():
     if sys.argv[1:] == ["--cases"]:
         return run_cases()
     if sys.argv[1:] == ["--yuv-cases"]:
         return run_yuv_cases()
-    child = "--yuv-cases" if sys.argv[1:] == ["--yuv"] else "--cases"
+    if sys.argv[1:] == ["--resize-cases"]:
+        return run_resize_cases()
+    child = {"--yuv": "--yuv-cases", "--resize": "--resize-cases"}.get(
+        " ".join(sys.argv[1:]), "--cases")
     cmd = [sys.executable, os.path.abspath(__file__), child]
     try:
         rc = subprocess.run(cmd, timeout=TIMEOUT_S).returncode
