@@ -14,6 +14,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..preprocess import (IMAGENET_MEAN, IMAGENET_STD, PatchEmbedPreprocess,
+                          RaggedResizePatchEmbedPreprocess,
                           ResizePatchEmbedPreprocess,
                           Yuv420PatchEmbedPreprocess)
 
@@ -138,6 +139,26 @@ def vit_b16_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
     every batch and source size tried (profiles/README.md); images that
     already are ``image_size`` square are served faster by ``uint8_nhwc``
     (the resampling loader costs 1.6-2.0x there).
+    ``input_format="uint8_ragged"``: one request carries N photos of N
+    different sizes, as ``resnet50_servable`` takes them in the mode of the
+    same name. "images" is DT_UINT8 [total_bytes], the HWC pixels of the
+    images back to back with no padding, and "image_shapes" is DT_INT32
+    (N,2), row i being (H_i, W_i) (``preprocess.pack_ragged_images`` builds
+    both). Per image the shorter side is resized to ``image_size * 8 // 7``,
+    then a centre crop of ``image_size``, bilinear, in ONE launch of the same
+    kernel, whose resampling loader reads the source geometry per tile row
+    (``preprocess.RaggedResizePatchEmbedPreprocess``,
+    ``ops.image_u8_ragged_resize_patch_embed``); every image gets exactly the
+    tokens ``uint8_nhwc_resize`` gives it alone. The patch must be 16 or 32.
+    Measured on an MI355X (ViT-B/16, bf16, photos of 256..512 x 341..683):
+    the op took 47 us for 8 photos and 105 us for 32, against 142 and 561 us
+    for one dense launch per photo plus ``torch.cat`` and 110-120 and 147 us
+    for ``ops.image_u8_ragged_resize_to_float`` plus ``embed``. For a single
+    photo it is slower than the dense mode (34 against 18 us: the per-image
+    table is built on the host). On batches of one size the launch costs
+    0.99-1.03 of the dense one, inside the spread of the measurement, but the
+    table still costs 6-18 us per call: keep ``uint8_nhwc_resize`` for
+    same-size requests (profiles/README.md; Predict latency not measured).
 
     ``output_format="logits"`` / ``"topk"`` and ``top_k``: as for
     ``resnet50_servable`` (``postprocess.TopKClassification``).
@@ -147,10 +168,11 @@ def vit_b16_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
     from ..server import Servable
 
     if input_format not in ("float_nchw", "uint8_nhwc", "uint8_nhwc_resize",
-                            "nv12", "i420"):
+                            "uint8_ragged", "nv12", "i420"):
         raise ValueError(
             f"input_format must be 'float_nchw', 'uint8_nhwc', "
-            f"'uint8_nhwc_resize', 'nv12' or 'i420', got {input_format!r}")
+            f"'uint8_nhwc_resize', 'uint8_ragged', 'nv12' or 'i420', got "
+            f"{input_format!r}")
     yuv = input_format in ("nv12", "i420")
     if yuv_matrix != "bt601" and not yuv:
         raise ValueError(
@@ -165,8 +187,9 @@ def vit_b16_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
     postprocess = TopKClassification(top_k)
     cfg = VitConfig() if config is None else config
     resize = input_format == "uint8_nhwc_resize"
+    ragged = input_format == "uint8_ragged"
     # tokens from the kernel
-    u8 = input_format == "uint8_nhwc" or resize or yuv
+    u8 = input_format == "uint8_nhwc" or resize or ragged or yuv
 
     torch.manual_seed(seed)
     model = vit_b16(cfg).to(device=device, dtype=dtype).eval()
@@ -198,6 +221,14 @@ def vit_b16_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
             IMAGENET_STD, pos_embed=model.pos_embed,
             cls_token=model.cls_token, out_dtype=dtype, device=device,
             resize=size * 8 // 7, center_crop=size)}
+    elif ragged:
+        images_sig = (4, [-1])                              # DT_UINT8
+        preprocess = {("images", "image_shapes"):
+                      RaggedResizePatchEmbedPreprocess(
+            model.patch_embed.weight, model.patch_embed.bias, IMAGENET_MEAN,
+            IMAGENET_STD, pos_embed=model.pos_embed,
+            cls_token=model.cls_token, out_dtype=dtype, device=device,
+            resize=size * 8 // 7, center_crop=size)}
     elif u8:
         images_sig = (4, [-1, size, size, 3])               # DT_UINT8
         preprocess = {"images": PatchEmbedPreprocess(
@@ -207,6 +238,9 @@ def vit_b16_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
     else:
         images_sig = (1, [-1, 3, size, size])               # DT_FLOAT
         preprocess = None
+    sig_inputs = {"images": images_sig}
+    if ragged:
+        sig_inputs["image_shapes"] = (3, [-1, 2])           # DT_INT32
     if topk:
         outputs = {"scores": (1, [-1, postprocess.k]),      # DT_FLOAT
                    "classes": (3, [-1, postprocess.k])}     # DT_INT32
@@ -216,7 +250,7 @@ def vit_b16_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
         fn,
         signature={
             "method_name": "tensorflow/serving/predict",
-            "inputs": {"images": images_sig},
+            "inputs": sig_inputs,
             "outputs": outputs,
         },
         preprocess=preprocess,

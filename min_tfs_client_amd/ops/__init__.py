@@ -601,6 +601,98 @@ def _first_bad(mask):
     return int(idx[0]) if idx.size else None
 
 
+def _ragged_data(name, data):
+    """The checks of a packed ragged buffer."""
+    if not isinstance(data, torch.Tensor):
+        raise ValueError(f"{name} expects a torch tensor")
+    if data.dtype != torch.uint8:
+        raise ValueError(f"{name} expects uint8 pixels, got {data.dtype}")
+    if data.dim() != 1:
+        raise ValueError(
+            f"{name} expects a flat [total_bytes] tensor, got rank "
+            f"{data.dim()}")
+    if not data.is_contiguous():
+        raise ValueError(f"{name} expects a contiguous tensor")
+
+
+def _ragged_geometry(name, data, shapes, sizes, out_size, origins, C):
+    """The per-image checks that the ragged ops share, for ``C`` channels:
+    ``(N, Hc, Wc, shp, siz, org, offsets)``, int64 numpy ``[N,2]`` arrays of
+    the input sizes, resized sizes and crop origins and the ``[N]`` byte
+    offsets of the images in ``data``."""
+    import numpy as np
+
+    if isinstance(shapes, torch.Tensor):
+        shapes = shapes.cpu().numpy()      # device tensor: synchronizing D2H
+    try:
+        shp = np.asarray(shapes)
+    except (TypeError, ValueError):
+        shp = None
+    if shp is not None and shp.size == 0 and shp.ndim <= 2:
+        shp = np.zeros((0, 2), dtype=np.int64)         # [] or [0,2]
+    if shp is None or shp.dtype.kind not in "iu" or shp.ndim != 2 or \
+            shp.shape[1] != 2:
+        raise ValueError(
+            f"{name}: shapes must be integer [N,2] rows of (H, W), got "
+            f"{shapes!r}")
+    shp = shp.astype(np.int64)
+    N = int(shp.shape[0])
+    try:
+        Hc, Wc = (int(d) for d in out_size)
+    except (TypeError, ValueError):
+        raise ValueError(
+            f"out_size must be (H, W), got {out_size!r}") from None
+    if not (1 <= Hc <= RESIZE_MAX_SIDE and 1 <= Wc <= RESIZE_MAX_SIDE):
+        raise ValueError(
+            f"{name}: out_size sides must be in 1..{RESIZE_MAX_SIDE}, got "
+            f"{Hc}x{Wc}")
+    siz = _ragged_pairs(sizes, N, "sizes", name)
+    org = (np.zeros((N, 2), dtype=np.int64) if origins is None
+           else _ragged_pairs(origins, N, "origins", name))
+
+    for label, arr in (("input", shp), ("resized", siz)):
+        bad = _first_bad(((arr < 1) | (arr > RESIZE_MAX_SIDE)).any(axis=1))
+        if bad is not None:
+            raise ValueError(
+                f"{name}: image {bad}: {label} sides must be in "
+                f"1..{RESIZE_MAX_SIDE}, got {int(arr[bad, 0])}x"
+                f"{int(arr[bad, 1])}")
+    nbytes = shp[:, 0] * shp[:, 1] * C
+    total = int(nbytes.sum())
+    if total != data.numel():
+        raise ValueError(
+            f"{name}: shapes describe {total} bytes ({N} images, {C} "
+            f"channels) but data has {data.numel()}")
+    bad = _first_bad((org < 0).any(axis=1) | (org[:, 0] + Hc > siz[:, 0]) |
+                     (org[:, 1] + Wc > siz[:, 1]))
+    if bad is not None:
+        raise ValueError(
+            f"{name}: image {bad}: crop window (top={int(org[bad, 0])}, "
+            f"left={int(org[bad, 1])}, {Hc}x{Wc}) is not inside the resized "
+            f"image {int(siz[bad, 0])}x{int(siz[bad, 1])}")
+    offsets = np.zeros(N, dtype=np.int64)
+    np.cumsum(nbytes[:-1], out=offsets[1:])
+    return N, Hc, Wc, shp, siz, org, offsets
+
+
+def _ragged_table(shp, siz, org, offsets, pinned):
+    """The ragged kernels' per-image table, a CPU int32 ``[N,8]`` tensor:
+    offset (int64 as two little-endian words), Hin, Win, top, left, bits of
+    rh, bits of rw."""
+    import numpy as np
+
+    N = int(shp.shape[0])
+    table = torch.empty((N, 8), dtype=torch.int32,
+                        pin_memory=N > 0 and pinned)
+    t = table.numpy()
+    t[:, 0:2] = offsets.astype("<i8").view("<i4").reshape(N, 2)
+    t[:, 2:4] = shp
+    t[:, 4:6] = org
+    # Python-double division rounded once to fp32, as the dense op does
+    t[:, 6:8] = (shp / siz).astype(np.float32).view(np.int32)
+    return table
+
+
 def image_u8_ragged_resize_to_float(data, shapes, sizes, out_size, mean, std,
                                     origins=None, out_dtype=None,
                                     layout="nchw", pixel_scale=1.0 / 255.0,
@@ -655,8 +747,6 @@ def image_u8_ragged_resize_to_float(data, shapes, sizes, out_size, mean, std,
     ``sizes`` / ``origins`` of the wrong shape; a crop window not inside an
     image's resized size; a bad ``layout`` or ``out_dtype``. ``N == 0`` with
     empty ``data`` returns an empty tensor of the output shape."""
-    import numpy as np
-
     name = "image_u8_ragged_resize_to_float"
     if out_dtype is None:
         out_dtype = torch.float32
@@ -665,16 +755,7 @@ def image_u8_ragged_resize_to_float(data, shapes, sizes, out_size, mean, std,
     if out_dtype not in (torch.float32, torch.bfloat16, torch.float16):
         raise ValueError(
             f"out_dtype must be float32, bfloat16 or float16, got {out_dtype}")
-    if not isinstance(data, torch.Tensor):
-        raise ValueError(f"{name} expects a torch tensor")
-    if data.dtype != torch.uint8:
-        raise ValueError(f"{name} expects uint8 pixels, got {data.dtype}")
-    if data.dim() != 1:
-        raise ValueError(
-            f"{name} expects a flat [total_bytes] tensor, got rank "
-            f"{data.dim()}")
-    if not data.is_contiguous():
-        raise ValueError(f"{name} expects a contiguous tensor")
+    _ragged_data(name, data)
     if len(mean) != len(std):
         raise ValueError(
             f"mean has {len(mean)} entries but std has {len(std)}")
@@ -682,70 +763,13 @@ def image_u8_ragged_resize_to_float(data, shapes, sizes, out_size, mean, std,
     if not 1 <= C <= 4:
         raise ValueError(f"{name} supports 1..4 channels, got {C}")
 
-    if isinstance(shapes, torch.Tensor):
-        shapes = shapes.cpu().numpy()      # device tensor: synchronizing D2H
-    try:
-        shp = np.asarray(shapes)
-    except (TypeError, ValueError):
-        shp = None
-    if shp is not None and shp.size == 0 and shp.ndim <= 2:
-        shp = np.zeros((0, 2), dtype=np.int64)         # [] or [0,2]
-    if shp is None or shp.dtype.kind not in "iu" or shp.ndim != 2 or \
-            shp.shape[1] != 2:
-        raise ValueError(
-            f"{name}: shapes must be integer [N,2] rows of (H, W), got "
-            f"{shapes!r}")
-    shp = shp.astype(np.int64)
-    N = int(shp.shape[0])
-    try:
-        Hc, Wc = (int(d) for d in out_size)
-    except (TypeError, ValueError):
-        raise ValueError(
-            f"out_size must be (H, W), got {out_size!r}") from None
-    if not (1 <= Hc <= RESIZE_MAX_SIDE and 1 <= Wc <= RESIZE_MAX_SIDE):
-        raise ValueError(
-            f"{name}: out_size sides must be in 1..{RESIZE_MAX_SIDE}, got "
-            f"{Hc}x{Wc}")
-    siz = _ragged_pairs(sizes, N, "sizes", name)
-    org = (np.zeros((N, 2), dtype=np.int64) if origins is None
-           else _ragged_pairs(origins, N, "origins", name))
-
-    for label, arr in (("input", shp), ("resized", siz)):
-        bad = _first_bad(((arr < 1) | (arr > RESIZE_MAX_SIDE)).any(axis=1))
-        if bad is not None:
-            raise ValueError(
-                f"{name}: image {bad}: {label} sides must be in "
-                f"1..{RESIZE_MAX_SIDE}, got {int(arr[bad, 0])}x"
-                f"{int(arr[bad, 1])}")
-    nbytes = shp[:, 0] * shp[:, 1] * C
-    total = int(nbytes.sum())
-    if total != data.numel():
-        raise ValueError(
-            f"{name}: shapes describe {total} bytes ({N} images, {C} "
-            f"channels) but data has {data.numel()}")
-    bad = _first_bad((org < 0).any(axis=1) | (org[:, 0] + Hc > siz[:, 0]) |
-                     (org[:, 1] + Wc > siz[:, 1]))
-    if bad is not None:
-        raise ValueError(
-            f"{name}: image {bad}: crop window (top={int(org[bad, 0])}, "
-            f"left={int(org[bad, 1])}, {Hc}x{Wc}) is not inside the resized "
-            f"image {int(siz[bad, 0])}x{int(siz[bad, 1])}")
+    N, Hc, Wc, shp, siz, org, offsets = _ragged_geometry(
+        name, data, shapes, sizes, out_size, origins, C)
     scale, bias = normalization_constants(mean, std, pixel_scale)
-    offsets = np.zeros(N, dtype=np.int64)
-    np.cumsum(nbytes[:-1], out=offsets[1:])
 
     if data.is_cuda:
         native = require_native()
-        # the kernel's per-image table, int32 [N,8]: offset (int64 as two
-        # little-endian words), Hin, Win, top, left, bits of rh, bits of rw
-        table = torch.empty((N, 8), dtype=torch.int32,
-                            pin_memory=N > 0 and not antialias)
-        t = table.numpy()
-        t[:, 0:2] = offsets.astype("<i8").view("<i4").reshape(N, 2)
-        t[:, 2:4] = shp
-        t[:, 4:6] = org
-        # Python-double division rounded once to fp32, as the dense op does
-        t[:, 6:8] = (shp / siz).astype(np.float32).view(np.int32)
+        table = _ragged_table(shp, siz, org, offsets, not antialias)
         if antialias:
             # the entry reads these rows on the host and ships its own table
             return native.u8_ragged_resize_aa_normalize(
@@ -1102,6 +1126,81 @@ def _image_u8_resize_patch_embed(images, size, wk, bias_f, patch, crop,
     lo = (v - hi).bfloat16().float()
     return _patch_embed_eager(hi + lo, wk, bias_f, P, pos_embed, cls_token,
                               out_dtype)
+
+
+def image_u8_ragged_resize_patch_embed(data, shapes, sizes, out_size, wk,
+                                       bias_f, patch, origins=None,
+                                       pos_embed=None, cls_token=None,
+                                       out_dtype=None):
+    """Fused ViT patch embedding of a ragged batch: N RGB images of N
+    different sizes, packed back to back with no padding, are each resized
+    and cropped to one shared window and go to tokens ``[N,T,D]``, in one
+    kernel launch.
+
+    ``data``, ``shapes``, ``sizes``, ``out_size`` and ``origins`` are those
+    of :func:`image_u8_ragged_resize_to_float` with ``C = 3`` (``shapes`` is
+    read on the host); ``out_size = (Hc,Wc)`` holds positive multiples of
+    ``patch``, which is 16 or 32. Every other argument is that of
+    :func:`image_u8_resize_patch_embed`. The contract, on the device and bit
+    for bit, for every image ``i`` (and every tile of the kernel)::
+
+        out[i] == image_u8_resize_patch_embed(
+                      data[off_i : off_i + H_i*W_i*3].view(1,H_i,W_i,3),
+                      sizes[i], wk, bias_f, patch,
+                      (top_i, left_i, Hc, Wc), pos_embed, cls_token,
+                      out_dtype)[0]
+
+    CPU tensors run exactly this loop over the dense op's eager path. Device
+    tensors run the gfx950 kernel only (no eager fallback), whose resampling
+    loader reads the source geometry per tile row: the host builds the
+    per-image table of :func:`image_u8_ragged_resize_to_float` and copies it
+    on the current stream from a pinned buffer. Deterministic.
+
+    Invalid arguments raise ``ValueError`` on both paths, before any launch,
+    and name the image at fault, as :func:`image_u8_ragged_resize_to_float`
+    does. ``N == 0`` with empty ``data`` returns an empty ``[0,T,D]``."""
+    return _image_u8_ragged_resize_patch_embed(
+        data, shapes, sizes, out_size, wk, bias_f, patch, origins, pos_embed,
+        cls_token, out_dtype, 0)
+
+
+def _image_u8_ragged_resize_patch_embed(data, shapes, sizes, out_size, wk,
+                                        bias_f, patch, origins, pos_embed,
+                                        cls_token, out_dtype, tile):
+    """:func:`image_u8_ragged_resize_patch_embed` with the kernel's tile
+    forced, as :func:`_image_u8_patch_embed`."""
+    name = "image_u8_ragged_resize_patch_embed"
+    if isinstance(patch, bool) or patch not in RESIZE_PATCH_EMBED_PATCHES:
+        raise ValueError(
+            f"{name}: patch must be one of {RESIZE_PATCH_EMBED_PATCHES}, got "
+            f"{patch!r}")
+    P = int(patch)
+    _ragged_data(name, data)
+    N, Hc, Wc, shp, siz, org, offsets = _ragged_geometry(
+        name, data, shapes, sizes, out_size, origins, 3)
+    out_dtype, T, D = _patch_embed_operands(
+        name, data, Hc, Wc, P, wk, bias_f, pos_embed, cls_token, out_dtype)
+    if N == 0:
+        return torch.empty((0, T, D), dtype=out_dtype, device=data.device)
+    if data.is_cuda:
+        native = require_native()
+        # pinned source: the copy is queued on the current stream and the
+        # caching host allocator keeps the buffer until it has completed
+        table_dev = _ragged_table(shp, siz, org, offsets, True).to(
+            data.device, non_blocking=True)
+        return native.u8_ragged_resize_patch_embed(
+            data, table_dev, Hc, Wc, wk, bias_f, P, pos_embed, cls_token,
+            out_dtype, int(tile))
+    outs = []
+    for i in range(N):
+        h, w = int(shp[i, 0]), int(shp[i, 1])
+        off = int(offsets[i])
+        outs.append(_image_u8_resize_patch_embed(
+            data[off:off + h * w * 3].view(1, h, w, 3),
+            (int(siz[i, 0]), int(siz[i, 1])), wk, bias_f, P,
+            (int(org[i, 0]), int(org[i, 1]), Hc, Wc), pos_embed, cls_token,
+            out_dtype, 0))
+    return torch.cat(outs)
 
 
 def masked_mean_pool(hidden, mask=None, normalize=False):

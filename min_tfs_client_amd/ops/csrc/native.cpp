@@ -87,6 +87,12 @@ at::Tensor u8_resize_patch_embed(const at::Tensor& images, double rh,
                                  const c10::optional<at::Tensor>& pos,
                                  const c10::optional<at::Tensor>& cls,
                                  at::ScalarType out_dtype, int64_t tile);
+at::Tensor u8_ragged_resize_patch_embed(
+    const at::Tensor& data, const at::Tensor& table, int64_t Hc, int64_t Wc,
+    const at::Tensor& wk, const at::Tensor& bias, int64_t patch,
+    const c10::optional<at::Tensor>& pos,
+    const c10::optional<at::Tensor>& cls, at::ScalarType out_dtype,
+    int64_t tile);
 at::Tensor dequantize_q8(const at::Tensor& in, double scale, double zp);
 void copy_device_to_host_ptr(const at::Tensor& src, void* dst, size_t n,
                              int mode);
@@ -733,6 +739,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("u8_resize_patch_embed", &mi355x::u8_resize_patch_embed,
         py::arg("images"), py::arg("rh"), py::arg("rw"), py::arg("top"),
         py::arg("left"), py::arg("crop_h"), py::arg("crop_w"), py::arg("wk"),
+        py::arg("bias"), py::arg("patch"), py::arg("pos"), py::arg("cls"),
+        py::arg("out_dtype"), py::arg("tile") = 0);
+  m.def("u8_ragged_resize_patch_embed",
+        &mi355x::u8_ragged_resize_patch_embed, py::arg("data"),
+        py::arg("table"), py::arg("crop_h"), py::arg("crop_w"), py::arg("wk"),
         py::arg("bias"), py::arg("patch"), py::arg("pos"), py::arg("cls"),
         py::arg("out_dtype"), py::arg("tile") = 0);
   m.def("quantize_q8", &mi355x::quantize_q8, py::arg("input"),

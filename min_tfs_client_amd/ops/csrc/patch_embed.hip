@@ -175,6 +175,64 @@
 //    of the time of image_u8_resize_to_float + VisionTransformer.embed; the
 //    identity size costs 1.6-2.0 of the RGB kernel (the second MFMA piece,
 //    the bf16 tile and the blend). profiles/README.md.
+//
+// Ragged batches into the resampling loader (PeGeomRagged, P = 16 and 32): N
+// RGB images of N sizes, HWC, back to back in one flat buffer; the crop
+// window Hc x Wc is shared, so M = N*Hp*Wp, the flat token index, the tiles,
+// the tile rule and the workgroup order are the dense loader's. What the
+// dense loader reads from the kernel arguments (Hin, Win, rh, rw, top, left,
+// n * Hin * Win * 3) is per image here, in a device table of int32 [N,8] rows
+// (PeRaggedEntry, the table of the ragged resize ingest in pack_kernels.hip).
+// The loader body is one: its geometry is a policy (PeGeomDense /
+// PeGeomRagged), and the dense instantiations compile to what they were
+// (same registers, LDS and occupancy as above).
+//  * Work split: the prologue thread of a tile row (tid < BM) works out the
+//    row's image from the flat token index, as before, and reads that image's
+//    32-byte entry once. Offset and crop origin go where the dense loader
+//    keeps them (row_pix, row_aux); (Hin, Win, rh, rw) go to a 16-byte slot
+//    of a fourth row table in LDS. Geometry is per ROW, not per tile: a tile
+//    of one-patch images has a different image on every row. After the
+//    barrier each thread, which owns one unit of one row for the whole K
+//    loop, lifts its row's slot into four registers in init(); load() and
+//    store() never touch the table again. Rows past M keep a 1 x 1 geometry,
+//    gather nothing and blend zero registers, as in the dense loader.
+//  * Cost (hipcc, ROCm 7.2): large tile 206 VGPRs + 32 AGPRs (dense 186 +
+//    32: the four values, and address arithmetic that was scalar and is now
+//    per lane), small tile 84 + 4 (dense 80 + 4), no scratch; occupancy 2 / 5
+//    waves per SIMD, the dense instantiations' (238 of the 256 registers of
+//    occupancy 2). LDS: 64 x 16 B more, 52.5 KB (large), 26.3 KB (small).
+//  * Reads stay inside the buffer: src_last is the last 8 bytes of the WHOLE
+//    packed buffer. resize_tap clamps y into [0, Hin_i) and x0 into
+//    [0, Win_i), so a gather starts at a = off_i + (y * Win_i + x0) * 3 <=
+//    off_i + Hin_i * Win_i * 3 - 3 <= bytes - 3; min(a, src_last) keeps the 8
+//    bytes inside the buffer and store() shifts by a - src_last <= 5. The
+//    first 3 bytes used are always pixel x0 of image i. The next 3 are pixel
+//    x0 + 1 of the same row when x1 = x0 + 1. When x1 == x0 (the right edge)
+//    they are the next row's, at an image's last pixel now the NEXT IMAGE's
+//    first bytes, or zeros shifted in at the end of the buffer: finite in
+//    every case, and the weight is replaced by 0, so the blend is p00, what
+//    p00 + wx * (p00 - p00) gives. A batch under 8 bytes is copied into 8 on
+//    the host. The host op validates every entry against the buffer size
+//    (sum of H_i * W_i * 3 == bytes) before the launch; the kernel trusts
+//    the table.
+//  * Every image's tokens are those of the dense launch on that image alone,
+//    bit for bit, at every tile: the taps depend on the image's own entry and
+//    the position in its resized image alone, and the MFMA loop, the B
+//    fragments and the epilogue are untouched, so an output element still
+//    accumulates hi then lo of ascending 32-wide slabs into one accumulator.
+//  * Measured on an MI355X (ViT-B/16, bf16 out, photos of mixed sizes,
+//    256..512 x 341..683 -> shorter side 256 -> crop 224; the launch alone on
+//    a device-resident table / the Python op with its host-built table): N =
+//    1: 16.3 / 34 us against 18 us for one dense call; N = 8: 41 / 47 us
+//    against 142 us for 8 dense launches + cat and 110-120 us for the ragged
+//    fp32 resize + embed; N = 32: 99 / 105 us against 561 us and 147 us. So
+//    the one launch wins from a few images on (3.0x and 5.3x against the
+//    loop at 8 and 32, 1.4-2.5x against resize-then-embed) and loses at N = 1
+//    to a single dense call, by the op's host-side table (about 18 us). On
+//    uniform batches (N x 384x512) this launch takes 0.99-1.03 of the dense
+//    resampling launch, inside the 4-8 % spread of the rounds; what remains
+//    is the op's table, 6-18 us per call, which same-size requests save by
+//    staying with the dense entry. profiles/README.md.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
@@ -206,6 +264,16 @@ constexpr int64_t kPeResizeLargeMinTiles = 256;
 typedef __bf16 pe_bf16x8 __attribute__((ext_vector_type(8)));
 typedef float pe_f32x4 __attribute__((ext_vector_type(4)));
 
+// One image of a ragged batch: a row of the int32 [N,8] table that
+// ops.image_u8_ragged_resize_to_float defines (U8RaggedEntry of
+// pack_kernels.hip), built and checked on the host.
+struct PeRaggedEntry {
+  int64_t offset;    // first byte of the image in the packed buffer
+  int Hin, Win, top, left;
+  float rh, rw;
+};
+static_assert(sizeof(PeRaggedEntry) == 32, "table rows are int32 [8]");
+
 struct PatchEmbedParams {
   const uint8_t* img;   // RGB pixels, or YUV 4:2:0 frames
   const uint16_t* wk;
@@ -226,6 +294,9 @@ struct PatchEmbedParams {
   int Hin, Win, top, left;
   float rh, rw;
   int64_t src_last;   // offset of the last 8 bytes of img
+  // ragged resampling loader only: img is the packed buffer, and Hin, Win,
+  // top, left, rh, rw above are unused: they are per image, in this table
+  const PeRaggedEntry* table;
 };
 
 struct PeOutF32 {
@@ -285,7 +356,7 @@ __device__ __forceinline__ pe_bf16x8 pe_byte_frag(const uint8_t* buf, int row,
 template <int P, int BM_>
 struct PeRgbLoader {
   static constexpr int BM = BM_, BK = 64, STRIDE = 80, PIECES = 1;
-  static constexpr bool kAux = false;
+  static constexpr bool kAux = false, kGeom = false;
   static constexpr int VEC = (P % 16 == 0) ? 16 : 2;   // bytes per A load
   static constexpr int ROWB = 3 * P;                   // bytes of a patch row
   static constexpr int UPR = BK / VEC;                 // load units per row
@@ -301,12 +372,12 @@ struct PeRgbLoader {
   // byte offset of the first pixel of patch (hp, wp) of image n
   static __device__ __forceinline__ void offsets(
       const PatchEmbedParams& p, int n, int hp, int wp, int64_t& pix,
-      int64_t&) {
+      int64_t&, int4&) {
     pix = ((int64_t(n) * p.H + int64_t(hp) * P) * p.W + int64_t(wp) * P) * 3;
   }
   __device__ __forceinline__ void init(const PatchEmbedParams&, int tid_,
                                        const int64_t* pix, const int64_t*,
-                                       const int* tok) {
+                                       const int4*, const int* tok) {
     row_pix = pix;
     row_tok = tok;
     tid = tid_;
@@ -382,6 +453,7 @@ struct PeYuvLoader {
   static_assert(P == 16 || P == 32, "a 42-byte patch row fits no unit");
   static constexpr int BM = BM_, BK = 96, STRIDE = 112, PIECES = 1;
   static constexpr bool kAux = true;       // the chroma offsets
+  static constexpr bool kGeom = false;
   static constexpr int UPR = kPeThreads / BM;          // units per tile row
   static_assert(UPR == 2 || UPR == 8, "one unit per thread");
   static constexpr int NR = (P == 16 && UPR == 2) ? 2 : 1;
@@ -399,7 +471,7 @@ struct PeYuvLoader {
   // offset of its first chroma sample (I420: in the U plane)
   static __device__ __forceinline__ void offsets(
       const PatchEmbedParams& p, int n, int hp, int wp, int64_t& pix,
-      int64_t& chr) {
+      int64_t& chr, int4&) {
     const int64_t fb = int64_t(n) * p.frame;
     const int64_t crow = int64_t(hp) * (P / 2);
     pix = fb + int64_t(hp) * P * p.W + int64_t(wp) * P;
@@ -409,7 +481,7 @@ struct PeYuvLoader {
   }
   __device__ __forceinline__ void init(const PatchEmbedParams& p, int tid,
                                        const int64_t* row_pix,
-                                       const int64_t* row_chr,
+                                       const int64_t* row_chr, const int4*,
                                        const int* row_tok) {
     const int r = tid / UPR, q = tid % UPR;
     const int kp = q * PX;                             // pixel of K in a step
@@ -543,13 +615,83 @@ __device__ __forceinline__ float pe_alone(float x) {
 // for any finite g, which is what p00 + wx * (p00 - p00) gives. A row past M
 // gathers nothing and keeps zero registers: their blend is +0 in both pieces
 // for any weights.
-template <int P, int BM_>
+//
+// GEO is where the source geometry (Hin, Win, rh, rw, and in the prologue the
+// image's offset and crop origin) comes from: PeGeomDense, one size per
+// launch, or PeGeomRagged, one size per tile row. The loader body is the same.
+
+// Dense: the geometry is launch-uniform, read from the kernel arguments where
+// it is used (scalar registers); the loader holds nothing.
+struct PeGeomDense {
+  static constexpr bool kTable = false;
+  // pix: byte offset of image n; aux: the output pixel (row << 32 | column)
+  // of the first pixel of the patch at (py0, px0) of the crop window
+  static __device__ __forceinline__ void offsets(
+      const PatchEmbedParams& p, int n, int py0, int px0, int64_t& pix,
+      int64_t& aux, int4&) {
+    pix = int64_t(n) * p.Hin * p.Win * 3;
+    aux = (int64_t(py0 + p.top) << 32) | int64_t(px0 + p.left);
+  }
+  __device__ __forceinline__ void set(const int4&) {}
+  __device__ __forceinline__ int Hin(const PatchEmbedParams& p) const {
+    return p.Hin;
+  }
+  __device__ __forceinline__ int Win(const PatchEmbedParams& p) const {
+    return p.Win;
+  }
+  __device__ __forceinline__ float rh(const PatchEmbedParams& p) const {
+    return p.rh;
+  }
+  __device__ __forceinline__ float rw(const PatchEmbedParams& p) const {
+    return p.rw;
+  }
+};
+
+// Ragged: image n of the packed buffer is described by p.table[n]. The
+// prologue thread of a tile row reads its image's entry once and leaves
+// (Hin, Win, bits of rh, bits of rw) in the row's slot of an LDS table; a
+// thread lifts its row's slot into four registers in init(). A row past M
+// keeps a 1 x 1 geometry that nothing reads through.
+struct PeGeomRagged {
+  static constexpr bool kTable = true;
+  int hin = 1, win = 1;
+  float rh_ = 1.f, rw_ = 1.f;
+  static __device__ __forceinline__ void offsets(
+      const PatchEmbedParams& p, int n, int py0, int px0, int64_t& pix,
+      int64_t& aux, int4& geo) {
+    const PeRaggedEntry e = p.table[n];
+    pix = e.offset;
+    aux = (int64_t(py0 + e.top) << 32) | int64_t(px0 + e.left);
+    geo = int4{e.Hin, e.Win, __float_as_int(e.rh), __float_as_int(e.rw)};
+  }
+  __device__ __forceinline__ void set(const int4& geo) {
+    hin = geo.x;
+    win = geo.y;
+    rh_ = __int_as_float(geo.z);
+    rw_ = __int_as_float(geo.w);
+  }
+  __device__ __forceinline__ int Hin(const PatchEmbedParams&) const {
+    return hin;
+  }
+  __device__ __forceinline__ int Win(const PatchEmbedParams&) const {
+    return win;
+  }
+  __device__ __forceinline__ float rh(const PatchEmbedParams&) const {
+    return rh_;
+  }
+  __device__ __forceinline__ float rw(const PatchEmbedParams&) const {
+    return rw_;
+  }
+};
+
+template <int P, int BM_, typename GEO>
 struct PeResizeLoader {
   static_assert(P == 16 || P == 32, "a 14-pixel patch row fits no unit");
   static constexpr int BM = BM_, BK = 96, PIECES = 2;
   static constexpr int PIECE = 2 * BK;                 // bytes of one piece
   static constexpr int STRIDE = 2 * PIECE + 16;        // 25 16-byte slots
   static constexpr bool kAux = true;                   // the pixel origins
+  static constexpr bool kGeom = GEO::kTable;           // per-row geometry
   static constexpr int UPR = kPeThreads / BM;          // units per tile row
   static_assert(UPR == 4 || UPR == 8, "one unit per thread");
   static constexpr int PX = 32 / UPR;                  // 8 or 4
@@ -561,24 +703,25 @@ struct PeResizeLoader {
   float wy;
   int d[2];              // (offset of source row y0 / y1) - src_last, clamped
   uint2 tap[2][PX];
+  GEO g;
 
-  // pix: byte offset of image n; aux: the output pixel (row << 32 | column)
-  // of the first pixel of patch (hp, wp) in the resized image
   static __device__ __forceinline__ void offsets(
       const PatchEmbedParams& p, int n, int hp, int wp, int64_t& pix,
-      int64_t& aux) {
-    pix = int64_t(n) * p.Hin * p.Win * 3;
-    aux = (int64_t(hp * P + p.top) << 32) | int64_t(wp * P + p.left);
+      int64_t& aux, int4& geo) {
+    GEO::offsets(p, n, hp * P, wp * P, pix, aux, geo);
   }
   __device__ __forceinline__ void init(const PatchEmbedParams&, int tid,
                                        const int64_t* row_pix,
                                        const int64_t* row_aux,
+                                       const int4* row_geo,
                                        const int* row_tok) {
     const int r = tid / UPR, q = tid % UPR;
     const int kp = q * PX;                             // pixel of K in a step
     const int j0 = (P == 16) ? kp / 16 : 0, px0 = (P == 16) ? kp % 16 : kp;
     lds_off = r * STRIDE + kp * 6;
     img = row_tok[r] >= 0 ? row_pix[r] : int64_t(-1);
+    if constexpr (GEO::kTable)
+      if (img >= 0) g.set(row_geo[r]);
     oy0 = int(row_aux[r] >> 32) + j0;
     ox0 = int(row_aux[r] & 0xffffffff) + px0;
     wy = 0.f;
@@ -591,11 +734,11 @@ struct PeResizeLoader {
       for (int i = 0; i < PX; ++i) tap[j][i] = uint2{0u, 0u};
     if (img < 0) return;
     int y[2];
-    resize_tap(oy0 + s * LROWS, 0, p.rh, p.Hin, y[0], y[1], wy);
+    resize_tap(oy0 + s * LROWS, 0, g.rh(p), g.Hin(p), y[0], y[1], wy);
     int64_t row[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      row[j] = img + int64_t(y[j]) * p.Win * 3;
+      row[j] = img + int64_t(y[j]) * g.Win(p) * 3;
       const int64_t over = row[j] - p.src_last;
       d[j] = int(over > -(int64_t(1) << 30) ? over : -(int64_t(1) << 30));
     }
@@ -603,7 +746,7 @@ struct PeResizeLoader {
     for (int i = 0; i < PX; ++i) {
       int x0, x1;
       float wx;
-      resize_tap(ox0 + i, 0, p.rw, p.Win, x0, x1, wx);
+      resize_tap(ox0 + i, 0, g.rw(p), g.Win(p), x0, x1, wx);
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         // row + x0*3 + 3 <= bytes of img, src_last >= 0: inside the tensor
@@ -621,7 +764,7 @@ struct PeResizeLoader {
     for (int i = 0; i < PX; ++i) {
       int x0, x1;
       float wx;
-      resize_tap(ox0 + i, 0, p.rw, p.Win, x0, x1, wx);
+      resize_tap(ox0 + i, 0, g.rw(p), g.Win(p), x0, x1, wx);
       wx = x1 == x0 ? 0.f : wx;
       uint32_t w[2][2];
 #pragma unroll
@@ -697,7 +840,12 @@ struct PeYuv {
 template <int P>
 struct PeResize {
   static constexpr int kLargeM = kPeResizeLargeM;
-  template <int BM> using Loader = PeResizeLoader<P, BM>;
+  template <int BM> using Loader = PeResizeLoader<P, BM, PeGeomDense>;
+};
+template <int P>
+struct PeRagged {
+  static constexpr int kLargeM = kPeResizeLargeM;
+  template <int BM> using Loader = PeResizeLoader<P, BM, PeGeomRagged>;
 };
 
 // a second int64 per tile row (chroma offset, pixel origin): LDS only in
@@ -706,6 +854,13 @@ template <int BM>
 __device__ __forceinline__ int64_t* pe_aux_table() {
   __shared__ int64_t row_aux[BM];
   return row_aux;
+}
+
+// the source geometry of a tile row's image (ragged loader only)
+template <int BM>
+__device__ __forceinline__ int4* pe_geo_table() {
+  __shared__ int4 row_geo[BM];
+  return row_geo;
 }
 
 template <typename LD, int TN, typename OUT>
@@ -721,6 +876,8 @@ patch_embed_kernel(const PatchEmbedParams p) {
   __shared__ int row_img[BM];
   int64_t* row_aux = nullptr;       // first chroma offset / pixel origin
   if constexpr (LD::kAux) row_aux = pe_aux_table<BM>();
+  int4* row_geo = nullptr;          // source geometry of the row's image
+  if constexpr (LD::kGeom) row_geo = pe_geo_table<BM>();
 
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int wm = wave >> 1, wn = wave & 1;
@@ -733,21 +890,23 @@ patch_embed_kernel(const PatchEmbedParams p) {
     const int m = m0 + tid;
     int tok = -1, n = 0;
     int64_t pix = 0, aux = 0;
+    int4 geo{0, 0, 0, 0};
     if (m < p.M) {
       n = m / p.HW;
       tok = m - n * p.HW;
       const int hp = tok / p.Wp, wp = tok - hp * p.Wp;
-      LD::offsets(p, n, hp, wp, pix, aux);
+      LD::offsets(p, n, hp, wp, pix, aux, geo);
     }
     row_pix[tid] = pix;
     if constexpr (LD::kAux) row_aux[tid] = aux;
+    if constexpr (LD::kGeom) row_geo[tid] = geo;
     row_tok[tid] = tok;
     row_img[tid] = n;
   }
   __syncthreads();
 
   LD ld;
-  ld.init(p, tid, row_pix, row_aux, row_tok);
+  ld.init(p, tid, row_pix, row_aux, row_geo, row_tok);
 
   // B rows of this lane; a block past D reads row D-1 and is never stored
   const uint16_t* b_row[TN];
@@ -870,7 +1029,7 @@ void launch_patch_embed_out(at::ScalarType out_dtype,
     launch_patch_embed<LD, TN, PeOutF16>(p, tiles, stream);
 }
 
-// SRC: PeRgb<P>, PeYuv<P, I420> or PeResize<P>
+// SRC: PeRgb<P>, PeYuv<P, I420>, PeResize<P> or PeRagged<P>
 template <typename SRC>
 void launch_patch_embed_tile(bool large, at::ScalarType out_dtype,
                              const PatchEmbedParams& p, int64_t tiles,
@@ -883,17 +1042,20 @@ void launch_patch_embed_tile(bool large, at::ScalarType out_dtype,
                            kPeSmallN / 32>(out_dtype, p, tiles, stream);
 }
 
-enum class PeSource { kRgb, kNv12, kI420, kResize };
+enum class PeSource { kRgb, kNv12, kI420, kResize, kRagged };
 
-// kResize only: the source geometry, checked by the caller
+// kResize: the source geometry, checked by the caller; kRagged: the device
+// table that holds it per image
 struct PeResizeArgs {
   int64_t Hin = 0, Win = 0, top = 0, left = 0;
   float rh = 0.f, rw = 0.f;
+  const PeRaggedEntry* table = nullptr;
 };
 
 // The part of the entry points below that does not depend on the pixel
-// format: `in` holds N images that give H x W pixels each (kResize: H x W is
-// the crop window, `rz` the source side) and was checked by the caller.
+// format: `in` holds N images that give H x W pixels each (kResize and
+// kRagged: H x W is the crop window, `rz` the source side) and was checked by
+// the caller.
 at::Tensor patch_embed_run(const char* who, const at::Tensor& in,
                            PeSource src, const Yuv420Coef& coef, int64_t N,
                            int64_t H, int64_t W, const at::Tensor& wk,
@@ -939,7 +1101,8 @@ at::Tensor patch_embed_run(const char* who, const at::Tensor& in,
   // 16-byte loads of pixels (P = 16, 32) and of weight fragments; the YUV
   // units' narrower loads are aligned to their width when the frames are;
   // the resampling loader gathers at any byte
-  const bool resize = src == PeSource::kResize;
+  const bool ragged = src == PeSource::kRagged;
+  const bool resize = src == PeSource::kResize || ragged;
   TORCH_CHECK_VALUE(
       (resize ||
        reinterpret_cast<uintptr_t>(in.const_data_ptr()) % 16 == 0) &&
@@ -981,11 +1144,19 @@ at::Tensor patch_embed_run(const char* who, const at::Tensor& in,
   p.Hin = int(rz.Hin); p.Win = int(rz.Win);
   p.top = int(rz.top); p.left = int(rz.left);
   p.rh = rz.rh; p.rw = rz.rw;
-  p.src_last = in.numel() - 8;            // kResize: the caller saw to >= 0
+  p.src_last = in.numel() - 8;            // resize: the caller saw to >= 0
+  p.table = rz.table;
 
   hipStream_t stream = at::hip::getCurrentHIPStream().stream();
   const bool p16 = patch == 16;
-  if (resize) {
+  if (ragged) {
+    if (p16)
+      launch_patch_embed_tile<PeRagged<16>>(large, out_dtype, p, tiles,
+                                            stream);
+    else
+      launch_patch_embed_tile<PeRagged<32>>(large, out_dtype, p, tiles,
+                                            stream);
+  } else if (resize) {
     if (p16)
       launch_patch_embed_tile<PeResize<16>>(large, out_dtype, p, tiles,
                                             stream);
@@ -1123,6 +1294,57 @@ at::Tensor u8_resize_patch_embed(const at::Tensor& images, double rh,
   rz.Hin = Hin; rz.Win = Win; rz.top = top; rz.left = left;
   rz.rh = float(rh); rz.rw = float(rw);
   return patch_embed_run(who, src, PeSource::kResize, Yuv420Coef{}, N, Hc, Wc,
+                         wk, bias, patch, pos, cls, out_dtype, tile, rz);
+}
+
+// The same from a ragged batch: ``data`` is the flat uint8 buffer of N RGB
+// images of N different sizes, HWC, back to back with no padding; ``table``
+// is the int32 [N,8] device image of PeRaggedEntry rows, one per image (its
+// offset, size, crop origin and ratios; the layout of
+// u8_ragged_resize_normalize), already on the device. Every image gives the
+// tokens of its own Hc x Wc window, exactly those of u8_resize_patch_embed on
+// that image alone. ops.image_u8_ragged_resize_patch_embed builds the table
+// on the host, validates every entry against the buffer size and copies it
+// on the current stream from a pinned buffer. The kernel trusts the table:
+// callers other than that op must make the same checks. Patches are 16 and
+// 32.
+at::Tensor u8_ragged_resize_patch_embed(
+    const at::Tensor& data, const at::Tensor& table, int64_t Hc, int64_t Wc,
+    const at::Tensor& wk, const at::Tensor& bias, int64_t patch,
+    const c10::optional<at::Tensor>& pos,
+    const c10::optional<at::Tensor>& cls, at::ScalarType out_dtype,
+    int64_t tile) {
+  const char* who = "u8_ragged_resize_patch_embed";
+  constexpr int64_t kMaxSide = 16384;
+  TORCH_CHECK_VALUE(data.is_cuda() && data.dim() == 1 &&
+                    data.is_contiguous() && data.scalar_type() == at::kByte,
+                    who, " expects a contiguous 1-D uint8 device tensor");
+  TORCH_CHECK_VALUE(table.is_cuda() &&
+                    table.get_device() == data.get_device() &&
+                    table.dim() == 2 && table.size(1) == 8 &&
+                    table.is_contiguous() && table.scalar_type() == at::kInt,
+                    who, ": table must be a contiguous int32 [N,8] tensor on "
+                    "the device of the input");
+  TORCH_CHECK_VALUE(
+      reinterpret_cast<uintptr_t>(table.const_data_ptr()) % 8 == 0, who,
+      ": table must be 8-byte aligned");
+  TORCH_CHECK_VALUE(patch == 16 || patch == 32, who,
+                    ": patch must be 16 or 32, got ", patch);
+  TORCH_CHECK_VALUE(Hc >= 1 && Wc >= 1 && Hc <= kMaxSide && Wc <= kMaxSide,
+                    who, ": bad crop window");
+  const int64_t N = table.size(0);
+  // an image is at least one pixel
+  TORCH_CHECK_VALUE(data.numel() >= 3 * N, who, ": table has ", N,
+                    " images but data only ", data.numel(), " bytes");
+  // the loader gathers 8 bytes at a time: a smaller batch gets a tail
+  at::Tensor src = data;
+  if (N > 0 && data.numel() < 8) {
+    src = at::zeros({8}, data.options());
+    src.narrow(0, 0, data.numel()).copy_(data);
+  }
+  PeResizeArgs rz;
+  rz.table = static_cast<const PeRaggedEntry*>(table.const_data_ptr());
+  return patch_embed_run(who, src, PeSource::kRagged, Yuv420Coef{}, N, Hc, Wc,
                          wk, bias, patch, pos, cls, out_dtype, tile, rz);
 }
 

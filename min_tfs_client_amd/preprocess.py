@@ -26,7 +26,9 @@ position embedding in one matrix-core kernel (``ops.image_u8_patch_embed``);
 ``Yuv420PatchEmbedPreprocess`` feeds the same kernel NV12 or I420 frames,
 converted while the tile is filled (``ops.image_yuv420_patch_embed``), and
 ``ResizePatchEmbedPreprocess`` images of any size, resized and centre-cropped
-while the tile is filled (``ops.image_u8_resize_patch_embed``).
+while the tile is filled (``ops.image_u8_resize_patch_embed``);
+``RaggedResizePatchEmbedPreprocess`` does that for a packed request of N
+images of N sizes in one launch (``ops.image_u8_ragged_resize_patch_embed``).
 """
 from __future__ import annotations
 
@@ -253,6 +255,39 @@ class Yuv420ImagePreprocess:
             matrix=self.matrix, antialias=self.antialias)
 
 
+def _ragged_windows(resize, center_crop, image_shapes):
+    """The per-image rules of the ragged hooks: ``(shapes, sizes, origins)``,
+    integer ``[N,2]`` arrays of every image's own size, its resized size and
+    the origin of its crop window (``resize`` / ``center_crop`` as
+    :class:`ImagePreprocess` keeps them)."""
+    shapes = image_shapes
+    if isinstance(shapes, torch.Tensor):
+        shapes = shapes.cpu().numpy()  # device tensor: synchronizing D2H
+    shapes = np.asarray(shapes)
+    if shapes.dtype.kind not in "iu" or shapes.ndim != 2 or \
+            shapes.shape[1] != 2:
+        raise ValueError(
+            "image_shapes must be integer [N,2] rows of (H, W), got "
+            f"dtype {shapes.dtype} shape {list(shapes.shape)}")
+    n = shapes.shape[0]
+    sizes = np.zeros((n, 2), dtype=np.int64)
+    origins = np.zeros((n, 2), dtype=np.int64)
+    for i in range(n):
+        h, w = int(shapes[i, 0]), int(shapes[i, 1])
+        if h < 1 or w < 1:
+            raise ValueError(
+                f"image {i}: sides must be positive, got {h}x{w}")
+        size = _resized_size(resize, h, w)
+        try:
+            window = _crop_window(center_crop, *size)
+        except ValueError as e:
+            raise ValueError(f"image {i} ({h}x{w}): {e}") from None
+        sizes[i] = size
+        if window is not None:
+            origins[i] = window[:2]
+    return shapes, sizes, origins
+
+
 class RaggedImagePreprocess:
     """N uint8 images of N different sizes -> one normalized float batch.
 
@@ -313,31 +348,8 @@ class RaggedImagePreprocess:
         x = _as_tensor(images)
         if self.device is not None and x.dtype == torch.uint8:
             x = x.to(self.device)
-        shapes = image_shapes
-        if isinstance(shapes, torch.Tensor):
-            shapes = shapes.cpu().numpy()  # device tensor: synchronizing D2H
-        shapes = np.asarray(shapes)
-        if shapes.dtype.kind not in "iu" or shapes.ndim != 2 or \
-                shapes.shape[1] != 2:
-            raise ValueError(
-                "image_shapes must be integer [N,2] rows of (H, W), got "
-                f"dtype {shapes.dtype} shape {list(shapes.shape)}")
-        n = shapes.shape[0]
-        sizes = np.zeros((n, 2), dtype=np.int64)
-        origins = np.zeros((n, 2), dtype=np.int64)
-        for i in range(n):
-            h, w = int(shapes[i, 0]), int(shapes[i, 1])
-            if h < 1 or w < 1:
-                raise ValueError(
-                    f"image {i}: sides must be positive, got {h}x{w}")
-            size = self._rule.resized_size(h, w)
-            try:
-                window = self._rule.crop_window(*size)
-            except ValueError as e:
-                raise ValueError(f"image {i} ({h}x{w}): {e}") from None
-            sizes[i] = size
-            if window is not None:
-                origins[i] = window[:2]
+        shapes, sizes, origins = _ragged_windows(
+            self.resize, self.center_crop, image_shapes)
         return ops.image_u8_ragged_resize_to_float(
             x, shapes, sizes, self.out_size, self.mean, self.std,
             origins=origins, out_dtype=self.out_dtype, layout=self.layout,
@@ -529,6 +541,60 @@ class ResizePatchEmbedPreprocess(PatchEmbedPreprocess):
         return ops.image_u8_resize_patch_embed(
             x, size, wk, bias_f, self.patch, crop=self.crop_window(*size),
             pos_embed=pos, cls_token=cls, out_dtype=self.out_dtype)
+
+
+class RaggedResizePatchEmbedPreprocess(PatchEmbedPreprocess):
+    """N uint8 RGB images of N different sizes -> ViT tokens ``[N,T,D]``, in
+    one launch of the patch-embedding kernel
+    (``ops.image_u8_ragged_resize_patch_embed``), whose resampling loader
+    takes the source geometry per tile row.
+
+    Called as ``pre(images, image_shapes)``, the packed buffer and the
+    ``[N,2]`` rows ``(H_i, W_i)`` of :class:`RaggedImagePreprocess`
+    (:func:`pack_ragged_images`); ``image_shapes`` is read on the host.
+    ``resize`` and ``center_crop`` follow that class's per-image rules and
+    must give one output size for all images, a multiple of the patch, which
+    is 16 or 32. Every image gets exactly the tokens that
+    :class:`ResizePatchEmbedPreprocess` gives it alone, bit for bit.
+    Everything else, the lazy refold included, is
+    :class:`PatchEmbedPreprocess`."""
+
+    def __init__(self, weight, bias, mean, std, pos_embed=None,
+                 cls_token=None, out_dtype=None,
+                 pixel_scale: float = 1.0 / 255.0, device=None,
+                 resize=None, center_crop=None):
+        super().__init__(weight, bias, mean, std, pos_embed=pos_embed,
+                         cls_token=cls_token, out_dtype=out_dtype,
+                         pixel_scale=pixel_scale, device=device)
+        if self.patch not in ops.RESIZE_PATCH_EMBED_PATCHES:
+            raise ValueError(
+                f"patch must be one of {ops.RESIZE_PATCH_EMBED_PATCHES} for "
+                f"resized input, got {self.patch}")
+        self.resize = _int_or_pair(resize, "resize")
+        crop = _int_or_pair(center_crop, "center_crop")
+        self.center_crop = (crop, crop) if isinstance(crop, int) else crop
+        if self.center_crop is not None:
+            self.out_size = self.center_crop
+        elif isinstance(self.resize, tuple):
+            self.out_size = self.resize
+        else:
+            raise ValueError(
+                "RaggedResizePatchEmbedPreprocess needs one output size for "
+                "all images: resize=(H, W), or center_crop with resize=int "
+                f"or alone; got resize={resize!r}, "
+                f"center_crop={center_crop!r}")
+
+    def __call__(self, images, image_shapes):
+        x = _as_tensor(images)
+        if self.device is not None and x.dtype == torch.uint8:
+            x = x.to(self.device)
+        shapes, sizes, origins = _ragged_windows(
+            self.resize, self.center_crop, image_shapes)
+        wk, bias_f, pos, cls = self.folded()
+        return ops.image_u8_ragged_resize_patch_embed(
+            x, shapes, sizes, self.out_size, wk, bias_f, self.patch,
+            origins=origins, pos_embed=pos, cls_token=cls,
+            out_dtype=self.out_dtype)
 
 
 def pack_ragged_images(images):

@@ -37,7 +37,9 @@ On-disk version-directory formats understood by the default loader:
                                "uint8_nhwc": raw pixels into the fused
                                patch-embedding kernel, "uint8_nhwc_resize":
                                pixels of any size, resized and cropped in
-                               the same kernel, or "nv12" / "i420": YUV
+                               the same kernel, "uint8_ragged": N images
+                               of N sizes in one request and one launch of
+                               that kernel, or "nv12" / "i420": YUV
                                4:2:0 frames into the same kernel),
                                "yuv_matrix" (with the YUV modes),
                                "output_format" ("logits" or "topk") and

@@ -5,6 +5,7 @@ composed chain a user would run without it, one GPU.
     python tools/bench_patch_embed.py          # JSON lines
     python tools/bench_patch_embed.py --yuv    # NV12 / I420 input, see below
     python tools/bench_patch_embed.py --resize # resize + crop input, see below
+    python tools/bench_patch_embed.py --ragged # mixed sizes, one launch
 
 The parent process never touches the GPU; the timings run in one fresh child
 process under a time limit, and the tool exits non-zero if it fails.
@@ -43,6 +44,19 @@ and fp32, per tile, against ``two_step_ms``, what a user runs without it:
 224x224 rows are the identity-size call against ``image_u8_patch_embed``
 (``rgb_*_ms``): the cost of the second MFMA piece and the bf16 tile.
 ``max_over_min_round`` is the largest spread of one timing over the rounds.
+
+``--ragged``: ``ops.image_u8_ragged_resize_patch_embed`` on N = 1, 8 and 32
+seeded photos of mixed sizes (256..512 x 341..683, both orientations, shorter
+side to 256, centre crop 224, bf16), per tile (``ragged_*_ms``, the whole
+Python op: checks, table, pinned copy, launch) and ``kernel_rule_ms``, the
+launch alone on a device-resident table, against what a user runs without it:
+``loop_ms``, N dense batch-1 ``image_u8_resize_patch_embed`` calls plus
+``torch.cat``, and ``two_step_ms``, ``ops.image_u8_ragged_resize_to_float``
+then ``VisionTransformer.embed``. The ``uniform_*`` columns are the control
+on N images of ONE size (384x512): the ragged launch on a device-resident
+table against the dense resampling kernel on the stacked batch, per forced
+tile, which is what the per-row geometry costs. ``identical``: whether the
+ragged op and the loop (uniform: the dense kernel) gave the same bits.
 """
 import json
 import os
@@ -252,6 +266,114 @@ def run_resize_cases():
                 print(json.dumps(row), flush=True)
 
 
+def run_ragged_cases():
+    import numpy as np
+    import torch
+
+    from min_tfs_client_amd import ops
+    from min_tfs_client_amd.models import vit_b16
+    from min_tfs_client_amd.preprocess import IMAGENET_MEAN, IMAGENET_STD
+
+    dev, P, S, dtype = "cuda:0", 16, 224, torch.bfloat16
+    native = ops.require_native()
+    torch.manual_seed(0)
+    model = vit_b16().to(dev).eval()
+    wk, bias_f = ops.patch_embed_fold(
+        model.patch_embed.weight, model.patch_embed.bias, IMAGENET_MEAN,
+        IMAGENET_STD)
+    pos = model.pos_embed.detach().float()[0].contiguous()
+    cls = model.cls_token.detach().float().reshape(-1)
+    m = model.to(dtype)
+    g = torch.Generator().manual_seed(0)
+    rng = np.random.default_rng(0)
+
+    def geometry(shapes):
+        """shorter side to 256, centre crop 224: sizes, origins, table"""
+        sizes = [(256, 256 * w // h) if h <= w else (256 * h // w, 256)
+                 for h, w in shapes]
+        origins = [((hr - S) // 2, (wr - S) // 2) for hr, wr in sizes]
+        shp = np.array(shapes, dtype=np.int64)
+        nbytes = shp[:, 0] * shp[:, 1] * 3
+        offsets = np.concatenate(([0], np.cumsum(nbytes[:-1])))
+        table = ops._ragged_table(
+            shp, np.array(sizes), np.array(origins), offsets, True).to(dev)
+        return sizes, origins, [int(o) for o in offsets], table
+
+    for N in (1, 8, 32):
+        # photos of mixed sizes and both orientations, and the uniform control
+        mixed = [(int(rng.integers(256, 513)), int(rng.integers(341, 684)))
+                 [::int(rng.choice((1, -1)))] for _ in range(N)]
+        row = {"case": f"{N}_mixed_bfloat16"}
+        spreads = []
+        for label, shapes in (("", mixed), ("uniform_", [(384, 512)] * N)):
+            sizes, origins, offs, table = geometry(shapes)
+            data = torch.randint(
+                0, 256, (sum(h * w * 3 for h, w in shapes),),
+                dtype=torch.uint8, generator=g).to(dev)
+            views = [data[o:o + h * w * 3].view(1, h, w, 3)
+                     for o, (h, w) in zip(offs, shapes)]
+
+            def ragged(tile=0):
+                return ops._image_u8_ragged_resize_patch_embed(
+                    data, shapes, sizes, (S, S), wk, bias_f, P, origins, pos,
+                    cls, dtype, tile)
+
+            def kernel(tile=0):       # the launch alone, table on the device
+                return native.u8_ragged_resize_patch_embed(
+                    data, table, S, S, wk, bias_f, P, pos, cls, dtype, tile)
+
+            def loop():
+                return torch.cat([ops._image_u8_resize_patch_embed(
+                    v, sz, wk, bias_f, P, (*o, S, S), pos, cls, dtype, 0)
+                    for v, sz, o in zip(views, sizes, origins)])
+
+            @torch.no_grad()
+            def two_step():
+                return m.embed(ops.image_u8_ragged_resize_to_float(
+                    data, shapes, sizes, (S, S), IMAGENET_MEAN, IMAGENET_STD,
+                    origins=origins, out_dtype=dtype))
+
+            def dense(tile=0):        # uniform sizes only
+                return ops._image_u8_resize_patch_embed(
+                    data.view(N, *shapes[0], 3), sizes[0], wk, bias_f, P,
+                    (*origins[0], S, S), pos, cls, dtype, tile)
+
+            if label:
+                names = [f"{k}_{t}" for t in ("small", "large")
+                         for k in ("kernel", "dense")]
+                fns = [lambda f=f, t=t: f(t) for t in (1, 2)
+                       for f in (kernel, dense)]
+                same = all(torch.equal(kernel(t), dense(t)) for t in (1, 2))
+            else:
+                names = [f"ragged_{t}" for t in TILES] + [
+                    "kernel_rule", "loop", "two_step"]
+                fns = [lambda t=t: ragged(t) for t in TILES.values()] + [
+                    kernel, loop, two_step]
+                same = torch.equal(ragged(), loop())
+                row["max_abs_diff_two_step"] = (
+                    ragged().float() - two_step().float()).abs().max().item()
+            rounds = [[time_kernel(f, 100, 10) for f in fns]
+                      for _ in range(5)]
+            for i, name in enumerate(names):
+                ts = sorted(r[i] for r in rounds)
+                row[f"{label}{name}_ms"] = round(ts[2], 4)
+                spreads.append(ts[-1] / ts[0])
+            row[f"{label}identical"] = same
+        row.update({
+            "loop_over_ragged": round(row["loop_ms"] / row["ragged_rule_ms"],
+                                      2),
+            "two_step_over_ragged": round(
+                row["two_step_ms"] / row["ragged_rule_ms"], 2),
+            "uniform_kernel_over_dense_small": round(
+                row["uniform_kernel_small_ms"] / row["uniform_dense_small_ms"],
+                2),
+            "uniform_kernel_over_dense_large": round(
+                row["uniform_kernel_large_ms"] / row["uniform_dense_large_ms"],
+                2),
+            "max_over_min_round": round(max(spreads), 2)})
+        print(json.dumps(row), flush=True)
+
+
 def main():
     if sys.argv[1:] == ["--cases"]:
         return run_cases()
@@ -259,7 +381,10 @@ def main():
         return run_yuv_cases()
     if sys.argv[1:] == ["--resize-cases"]:
         return run_resize_cases()
-    child = {"--yuv": "--yuv-cases", "--resize": "--resize-cases"}.get(
+    if sys.argv[1:] == ["--ragged-cases"]:
+        return run_ragged_cases()
+    child = {"--yuv": "--yuv-cases", "--resize": "--resize-cases",
+             "--ragged": "--ragged-cases"}.get(
         " ".join(sys.argv[1:]), "--cases")
     cmd = [sys.executable, os.path.abspath(__file__), child]
     try:
