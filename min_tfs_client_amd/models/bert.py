@@ -63,25 +63,41 @@ class BertEncoder(nn.Module):
             [BertLayer(cfg) for _ in range(cfg.layers)])
         self.pooler = nn.Linear(cfg.hidden, cfg.hidden)
 
-    def forward(self, input_ids, attention_mask=None):
+    def embed(self, input_ids, token_type_ids=None):
+        """ids (B,S) -> the encoder's input (B,S,H): token + position + type
+        embeddings, LayerNorm. ``token_type_ids`` None: all zero."""
         B, S = input_ids.shape
         if S > self.cfg.max_pos:
             raise ValueError(
                 f"sequence length {S} exceeds max_position_embeddings "
                 f"{self.cfg.max_pos}")
         pos_ids = torch.arange(S, device=input_ids.device)
-        x = self.tok(input_ids.long()) + self.pos(pos_ids) \
-            + self.typ(torch.zeros_like(input_ids.long()))
-        x = self.ln(x)
-        mask = None
-        if attention_mask is not None:
-            # additive mask: (B,1,1,S), 0 where attend, -inf where padded
-            m = attention_mask[:, None, None, :].to(x.dtype)
-            mask = (1.0 - m) * torch.finfo(x.dtype).min
+        x = self.tok(input_ids.long()) + self.pos(pos_ids)
+        # the types are built after the two gathers, as forward always did
+        x = x + self.typ(torch.zeros_like(input_ids.long())
+                         if token_type_ids is None else token_type_ids.long())
+        return self.ln(x)
+
+    @staticmethod
+    def additive_mask(attention_mask, dtype):
+        """(B,S) keep mask -> additive (B,1,1,S): 0 where attend, finfo.min
+        where padded; None stays None."""
+        if attention_mask is None:
+            return None
+        m = attention_mask[:, None, None, :].to(dtype)
+        return (1.0 - m) * torch.finfo(dtype).min
+
+    def forward_embedded(self, x, mask):
+        """The encoder blocks and the pooler on an embedded input."""
         for blk in self.blocks:
             x = blk(x, mask)
         pooled = torch.tanh(self.pooler(x[:, 0]))
         return x, pooled
+
+    def forward(self, input_ids, attention_mask=None):
+        x = self.embed(input_ids)
+        return self.forward_embedded(
+            x, self.additive_mask(attention_mask, x.dtype))
 
 
 def bert_base() -> BertEncoder:
@@ -90,8 +106,40 @@ def bert_base() -> BertEncoder:
 
 def bert_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
                   output_format: str = "hidden",
-                  normalize_embedding: bool = True):
+                  normalize_embedding: bool = True,
+                  input_format: str = "ids", config: BertConfig = None):
     """BERT-base Servable: inputs "input_ids"/"attention_mask" int32.
+
+    ``input_format="ids"`` (default): the encoder input is built by the
+    module's eager ``embed`` and ``additive_mask`` (about a dozen launches).
+    ``input_format="ids_fused"``: the same two inputs plus an optional
+    "token_type_ids" (DT_INT32 (B,S), for sentence pairs; absent: all zero).
+    Ids, types and mask go through ONE launch of the fused embedding kernel
+    (``ops.bert_embed``) on the module's own parameters, read at call time
+    (``load_state_dict`` needs no refold), then ``forward_embedded``.
+    ``input_format="ids_ragged"``: "input_ids" is DT_INT32 (total), the ids
+    of B sequences back to back with no padding, and "sequence_lengths" is
+    DT_INT32 (B) (``preprocess.pack_ragged_tokens`` builds both); an optional
+    flat "token_type_ids" as well. There is no "attention_mask": the same
+    launch (``ops.bert_embed_ragged``) pads to S = the longest sequence with
+    id 0 and derives the mask from the lengths, and the outputs have that S.
+    It equals ``"ids_fused"`` on the padded request bit for bit.
+
+    Numeric contract of the two fused modes: the three embedding rows are
+    summed in fp32 from the values as stored, LayerNorm is two-pass fp32
+    (biased variance, IEEE ``1/sqrt(var + eps)``) and the result is rounded
+    once, to the model's dtype; the additive mask is +0.0 where a position is
+    kept and ``finfo(dtype).min`` where it is not. In fp32 that differs from
+    ``"ids"`` by a few units in the last place, in bf16/f16 ``"ids"`` rounds
+    after every eager step and the fused modes are the closer to exact. They
+    are deterministic. An id outside the vocabulary, a type outside the type
+    vocabulary, a sequence longer than ``max_pos`` or lengths that do not sum
+    to the ids are INVALID_ARGUMENT naming the row; on the device a bad id
+    never indexes a table. That check costs one 4-byte synchronizing D2H
+    read per request (profiles/README.md has the measured cost).
+
+    ``config``: a ``BertConfig`` to build instead of BERT-base (tests serve a
+    one-layer model).
 
     ``output_format="hidden"`` (default): outputs "last_hidden_state"
     (B,S,768) + "pooled_output" (B,768), both DT_FLOAT.
@@ -109,42 +157,81 @@ def bert_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
         raise ValueError(
             f"output_format must be 'hidden' or 'sentence_embedding', got "
             f"{output_format!r}")
+    if input_format not in ("ids", "ids_fused", "ids_ragged"):
+        raise ValueError(
+            f"input_format must be 'ids', 'ids_fused' or 'ids_ragged', got "
+            f"{input_format!r}")
     embed = output_format == "sentence_embedding"
     normalize_embedding = bool(normalize_embedding)
+    fused = input_format == "ids_fused"
+    ragged = input_format == "ids_ragged"
 
     torch.manual_seed(seed)
-    model = bert_base().to(device=device, dtype=dtype).eval()
+    cfg = BertConfig() if config is None else config
+    model = BertEncoder(cfg).to(device=device, dtype=dtype).eval()
+
+    def on_device(value):
+        if value is None:
+            return None
+        if not isinstance(value, torch.Tensor):
+            value = torch.as_tensor(value)
+        return value.to(device=device)
+
+    def fused_embed(inputs):
+        """(encoder input, additive mask, pooling mask) from the fused
+        kernel, on the module's parameters as they are at call time."""
+        m = s.module
+        ids = on_device(inputs["input_ids"])
+        types = on_device(inputs.get("token_type_ids"))
+        tables = (m.tok.weight, m.pos.weight, m.typ.weight, m.ln.weight,
+                  m.ln.bias, m.ln.eps)
+        out_dtype = m.tok.weight.dtype
+        if ragged:
+            # read on the host: keep a host tensor on the host
+            x, add_mask = ops.bert_embed_ragged(
+                ids, inputs["sequence_lengths"], *tables,
+                token_type_ids=types, out_dtype=out_dtype)
+            return x, add_mask, add_mask[:, 0, 0, :] == 0
+        mask = on_device(inputs.get("attention_mask"))
+        x, add_mask = ops.bert_embed(
+            ids, *tables, attention_mask=mask, token_type_ids=types,
+            out_dtype=out_dtype)
+        return x, add_mask, mask
 
     @torch.no_grad()
     def fn(inputs):
-        ids = inputs["input_ids"]
-        mask = inputs.get("attention_mask")
-        if not isinstance(ids, torch.Tensor):
-            ids = torch.as_tensor(ids)
-        ids = ids.to(device=device)
-        if mask is not None:
-            if not isinstance(mask, torch.Tensor):
-                mask = torch.as_tensor(mask)
-            mask = mask.to(device=device)
-        hidden, pooled = s.module(ids, mask)
+        if fused or ragged:
+            x, add_mask, mask = fused_embed(inputs)
+            hidden, pooled = s.module.forward_embedded(x, add_mask)
+        else:
+            ids = on_device(inputs["input_ids"])
+            mask = on_device(inputs.get("attention_mask"))
+            hidden, pooled = s.module(ids, mask)
         if embed:
             return {"sentence_embedding": ops.masked_mean_pool(
                 hidden.contiguous(), mask, normalize_embedding)}
         return {"last_hidden_state": hidden.float(),
                 "pooled_output": pooled.float()}
 
+    H = cfg.hidden
     if embed:
-        outputs = {"sentence_embedding": (1, [-1, 768])}
+        outputs = {"sentence_embedding": (1, [-1, H])}
     else:
-        outputs = {"last_hidden_state": (1, [-1, -1, 768]),
-                   "pooled_output": (1, [-1, 768])}
-    s = Servable(
-        fn,
-        signature={
-            "method_name": "tensorflow/serving/predict",
-            "inputs": {"input_ids": (3, [-1, -1]),
-                       "attention_mask": (3, [-1, -1])},  # DT_INT32
-            "outputs": outputs,
-        })
+        outputs = {"last_hidden_state": (1, [-1, -1, H]),
+                   "pooled_output": (1, [-1, H])}
+    if ragged:
+        sig_inputs = {"input_ids": (3, [-1]),              # DT_INT32
+                      "sequence_lengths": (3, [-1]),
+                      "token_type_ids": (3, [-1])}
+    else:
+        sig_inputs = {"input_ids": (3, [-1, -1]),          # DT_INT32
+                      "attention_mask": (3, [-1, -1])}
+        if fused:
+            sig_inputs["token_type_ids"] = (3, [-1, -1])
+    signature = {"method_name": "tensorflow/serving/predict",
+                 "inputs": sig_inputs, "outputs": outputs}
+    if fused or ragged:
+        signature["optional_inputs"] = ["token_type_ids"]
+    s = Servable(fn, signature=signature)
     s.module = model
     return s

@@ -1203,6 +1203,336 @@ def _image_u8_ragged_resize_patch_embed(data, shapes, sizes, out_size, wk,
     return torch.cat(outs)
 
 
+BERT_EMBED_MAX_HIDDEN = 4096
+_FLOAT_DTYPES = ("float32", "bfloat16", "float16")
+
+
+def _bert_embed_operands(name, input_ids, ids_rank, tok, pos, typ, gamma,
+                         beta, token_type_ids, out_dtype):
+    """The checks that both BERT embedding ops share: ``(token_type_ids,
+    out_dtype)``, the types contiguous in the dtype of the ids."""
+    tables = (("tok", tok, 2), ("pos", pos, 2), ("typ", typ, 2),
+              ("gamma", gamma, 1), ("beta", beta, 1))
+    for label, t, rank in tables:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name}: {label} must be a torch tensor")
+        if t.dim() != rank:
+            raise ValueError(
+                f"{name}: {label} must have rank {rank}, got {t.dim()}")
+        if t.dtype != tok.dtype:
+            raise ValueError(
+                f"{name}: tables, gamma and beta share one dtype, but tok is "
+                f"{tok.dtype} and {label} is {t.dtype}")
+        if t.device != tok.device:
+            raise ValueError(
+                f"{name}: {label} is on {t.device} but tok is on "
+                f"{tok.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: {label} must be contiguous")
+    floats = tuple(getattr(torch, n) for n in _FLOAT_DTYPES)
+    if tok.dtype not in floats:
+        raise ValueError(
+            f"{name}: tables must be float32, bfloat16 or float16, got "
+            f"{tok.dtype}")
+    H = int(tok.shape[1])
+    if H % 8 or not 8 <= H <= BERT_EMBED_MAX_HIDDEN:
+        raise ValueError(
+            f"{name}: H must be a multiple of 8 in 8.."
+            f"{BERT_EMBED_MAX_HIDDEN}, got {H}")
+    if tok.shape[0] < 1 or typ.shape[0] < 1:
+        raise ValueError(f"{name}: tok and typ must have at least one row")
+    for label, t, _ in tables[1:]:
+        if t.shape[-1] != H:
+            raise ValueError(
+                f"{name}: {label} has {t.shape[-1]} columns but tok has {H}")
+    if out_dtype is None:
+        out_dtype = tok.dtype
+    if out_dtype not in floats:
+        raise ValueError(
+            f"out_dtype must be float32, bfloat16 or float16, got {out_dtype}")
+
+    def ids_like(label, t):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name}: {label} must be a torch tensor")
+        if t.dtype not in (torch.int32, torch.int64):
+            raise ValueError(
+                f"{name}: {label} must be int32 or int64, got {t.dtype}")
+        if t.dim() != ids_rank:
+            raise ValueError(
+                f"{name}: {label} must have rank {ids_rank}, got {t.dim()}")
+        if t.device != tok.device:
+            raise ValueError(
+                f"{name}: {label} is on {t.device} but tok is on "
+                f"{tok.device}")
+
+    ids_like("input_ids", input_ids)
+    if not input_ids.is_contiguous():
+        raise ValueError(f"{name}: input_ids must be contiguous")
+    if token_type_ids is not None:
+        ids_like("token_type_ids", token_type_ids)
+        if token_type_ids.shape != input_ids.shape:
+            raise ValueError(
+                f"{name}: token_type_ids has shape "
+                f"{list(token_type_ids.shape)} but input_ids has "
+                f"{list(input_ids.shape)}")
+        # the kernel reads both through one template parameter
+        token_type_ids = token_type_ids.to(input_ids.dtype).contiguous()
+    return token_type_ids, out_dtype
+
+
+def _bert_embed_bad(name, kind, where, value, bound):
+    what = "token_type_ids" if kind else "input_ids"
+    return ValueError(
+        f"{name}: {what}{where} = {value} is outside [0, {bound})")
+
+
+def _bert_embed_first_bad(input_ids, token_type_ids, vocab, type_vocab):
+    """CPU path: the lowest row whose id or type is out of range, as the
+    kernel reports it (the id first when both are bad): ``(kind, flat
+    index)`` or ``None``."""
+    bad = (input_ids < 0) | (input_ids >= vocab)
+    kind = torch.zeros_like(bad)
+    if token_type_ids is not None:
+        bad_t = (token_type_ids < 0) | (token_type_ids >= type_vocab)
+        kind = bad_t & ~bad
+        bad = bad | bad_t
+    flat = bad.reshape(-1).nonzero()
+    if flat.numel() == 0:
+        return None
+    i = int(flat[0])
+    return int(kind.reshape(-1)[i]), i
+
+
+def bert_embed(input_ids, tok, pos, typ, gamma, beta, eps,
+               attention_mask=None, token_type_ids=None, out_dtype=None):
+    """Fused BERT embedding ingest: token ids ``[B,S]`` -> ``(hidden,
+    additive_mask)``, the encoder's input ``[B,S,H]`` and its attention mask
+    ``[B,1,1,S]`` (``None`` when ``attention_mask`` is), in one launch.
+
+        x      = float(tok[id]) + float(pos[s]) + float(typ[type])   (fp32)
+        hidden = out_dtype(LayerNorm(x; gamma, beta, eps))
+        mask   = where(attention_mask != 0, +0.0, finfo(out_dtype).min)
+
+    The three rows are summed in fp32 from the values as stored, the
+    statistics are two-pass fp32 (mean, then the sum of squared deviations;
+    biased variance) with an IEEE ``1 / sqrt(var + eps)``, and the result is
+    rounded once, to ``out_dtype`` (default: the tables' dtype). The result
+    is deterministic: the same input gives bit-identical output on every run,
+    and a row's bits depend on its id, position and type only.
+
+    * ``input_ids``: int32 or int64 ``[B,S]``, contiguous, read as they are
+      (no cast). ``S <= pos.shape[0]``.
+    * ``tok [vocab,H]``, ``pos [max_pos,H]``, ``typ [type_vocab,H]``,
+      ``gamma [H]``, ``beta [H]``: contiguous float32, bfloat16 or float16,
+      all of one dtype, on the device of the ids. ``H`` is a multiple of 8
+      in 8..4096.
+    * ``attention_mask``: integer or bool ``[B,S]``; non-zero keeps.
+    * ``token_type_ids``: int32 or int64 ``[B,S]`` (``None``: all zero).
+
+    An id outside ``[0, vocab)`` or a type outside ``[0, type_vocab)`` is a
+    ``ValueError`` that names the batch row, the position, the value and the
+    bound. On the device such a value never indexes a table: the kernel
+    reads row 0 instead and reports the lowest bad row through a 4-byte
+    error slot, which this wrapper reads after the launch with one small
+    synchronizing D2H copy.
+
+    Device tensors run the gfx950 kernel only (no eager fallback); CPU
+    tensors use an eager expression with the same semantics, so CPU-only
+    servers work too. ``B == 0`` or ``S == 0`` returns empty tensors. Invalid
+    arguments raise ``ValueError`` on both paths."""
+    name = "bert_embed"
+    token_type_ids, out_dtype = _bert_embed_operands(
+        name, input_ids, 2, tok, pos, typ, gamma, beta, token_type_ids,
+        out_dtype)
+    B, S = (int(d) for d in input_ids.shape)
+    H = int(tok.shape[1])
+    if S > pos.shape[0]:
+        raise ValueError(
+            f"{name}: sequence length {S} exceeds max_position_embeddings "
+            f"{int(pos.shape[0])}")
+    mask = attention_mask
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor):
+            raise ValueError(f"{name}: attention_mask must be a torch tensor")
+        if tuple(mask.shape) != (B, S):
+            raise ValueError(
+                f"{name}: attention_mask must have shape {[B, S]}, got "
+                f"{list(mask.shape)}")
+        if mask.is_floating_point() or mask.is_complex():
+            raise ValueError(
+                f"{name}: attention_mask must be an integer or bool tensor, "
+                f"got {mask.dtype}")
+        if mask.device != tok.device:
+            raise ValueError(
+                f"{name}: attention_mask is on {mask.device} but tok is on "
+                f"{tok.device}")
+        if mask.dtype not in (torch.int32, torch.int64, torch.uint8,
+                              torch.bool):
+            mask = mask != 0
+        mask = mask.contiguous()
+    vocab, type_vocab = int(tok.shape[0]), int(typ.shape[0])
+    if B == 0 or S == 0:
+        hidden = torch.empty((B, S, H), dtype=out_dtype, device=tok.device)
+        return hidden, (None if mask is None else
+                        torch.empty((B, 1, 1, S), dtype=out_dtype,
+                                    device=tok.device))
+    if tok.is_cuda:
+        hidden, add_mask, code = require_native().bert_embed(
+            input_ids, None, B, S, mask, token_type_ids, tok, pos, typ,
+            gamma, beta, float(eps), 0, out_dtype, True)
+        if code >= 0:
+            b, s = divmod(code >> 1, S)
+            src = token_type_ids if code & 1 else input_ids
+            raise _bert_embed_bad(name, code & 1, f"[{b},{s}]",
+                                  int(src[b, s]),
+                                  type_vocab if code & 1 else vocab)
+        return hidden, add_mask
+    bad = _bert_embed_first_bad(input_ids, token_type_ids, vocab,
+                                type_vocab)
+    if bad is not None:
+        kind, i = bad
+        b, s = divmod(i, S)
+        src = token_type_ids if kind else input_ids
+        raise _bert_embed_bad(name, kind, f"[{b},{s}]", int(src[b, s]),
+                              type_vocab if kind else vocab)
+    import torch.nn.functional as F
+    x = F.embedding(input_ids, tok).float() + pos[:S].float()
+    x = x + (typ[0].float() if token_type_ids is None
+             else F.embedding(token_type_ids, typ).float())
+    hidden = F.layer_norm(x, (H,), gamma.float(), beta.float(),
+                          float(eps)).to(out_dtype)
+    if mask is None:
+        return hidden, None
+    zero = torch.zeros((), dtype=out_dtype)
+    low = torch.full((), torch.finfo(out_dtype).min, dtype=out_dtype)
+    return hidden, torch.where(mask != 0, zero, low)[:, None, None, :]
+
+
+def _bert_ragged_lengths(name, lengths, total, max_pos):
+    """``lengths`` as int64 numpy ``[B]``, each in 1..max_pos, summing to
+    ``total``; read on the host."""
+    import numpy as np
+
+    if isinstance(lengths, torch.Tensor):
+        lengths = lengths.cpu().numpy()    # device tensor: synchronizing D2H
+    try:
+        arr = np.asarray(lengths)
+    except (TypeError, ValueError):
+        arr = None
+    if arr is not None and arr.size == 0 and arr.ndim == 1:
+        arr = np.zeros((0,), dtype=np.int64)
+    if arr is None or arr.dtype.kind not in "iu" or arr.ndim != 1:
+        raise ValueError(
+            f"{name}: lengths must be integer [B], got {lengths!r}")
+    arr = arr.astype(np.int64)
+    bad = _first_bad((arr < 1) | (arr > max_pos))
+    if bad is not None:
+        raise ValueError(
+            f"{name}: sequence {bad}: length must be in 1..{max_pos} "
+            f"(max_position_embeddings), got {int(arr[bad])}")
+    ends = np.cumsum(arr)
+    bad = _first_bad(ends > total)
+    if bad is not None or int(arr.sum()) != total:
+        at = f"sequence {bad} ends past it" if bad is not None else \
+            f"sequence {len(arr) - 1} ends before it" if len(arr) else \
+            "there are no sequences"
+        raise ValueError(
+            f"{name}: lengths sum to {int(arr.sum())} but input_ids has "
+            f"{total} tokens: {at}")
+    return arr
+
+
+def bert_embed_ragged(input_ids, lengths, tok, pos, typ, gamma, beta, eps,
+                      token_type_ids=None, pad_id=0, out_dtype=None):
+    """:func:`bert_embed` of a ragged batch: B sequences of B lengths, their
+    ids back to back in ``input_ids [total]`` with no padding, go to
+    ``(hidden [B,S,H], additive_mask [B,1,1,S])`` with ``S = max(lengths)``,
+    in one launch of the same kernel.
+
+    * ``lengths``: integer ``[B]``, each in ``1..pos.shape[0]``, summing to
+      ``total``. Read on the **host**: a list, a numpy array or a CPU tensor
+      (a device tensor costs a small synchronizing D2H copy).
+    * ``token_type_ids``: flat like ``input_ids``; padded positions get
+      type 0.
+    * ``pad_id``: the id of positions at and past a sequence's length.
+
+    The contract, on the device and bit for bit::
+
+        ids  = full((B,S), pad_id);  ids[b, :len_b] = input_ids[off_b:...]
+        mask = arange(S)[None] < lengths[:, None]
+        out == bert_embed(ids, ..., attention_mask=mask,
+                          token_type_ids=<padded with 0>)
+
+    CPU tensors run exactly this. Device tensors run the gfx950 kernel only
+    (no eager fallback): the host builds an int32 ``(offset, length)`` table
+    and copies it on the current stream from a pinned buffer. Invalid
+    arguments raise ``ValueError`` on both paths, before any launch; a bad
+    length names its sequence, a bad id or type names its sequence, position,
+    value and bound, as in :func:`bert_embed`. ``B == 0`` with empty
+    ``input_ids`` returns empty tensors."""
+    import numpy as np
+
+    name = "bert_embed_ragged"
+    token_type_ids, out_dtype = _bert_embed_operands(
+        name, input_ids, 1, tok, pos, typ, gamma, beta, token_type_ids,
+        out_dtype)
+    vocab, type_vocab = int(tok.shape[0]), int(typ.shape[0])
+    try:
+        if isinstance(pad_id, bool):
+            raise TypeError
+        pad_id = operator.index(pad_id)
+    except TypeError:
+        raise ValueError(f"pad_id must be an integer, got {pad_id!r}") \
+            from None
+    if not 0 <= pad_id < vocab:
+        raise ValueError(
+            f"{name}: pad_id {pad_id} is outside [0, {vocab})")
+    total = int(input_ids.numel())
+    lens = _bert_ragged_lengths(name, lengths, total, int(pos.shape[0]))
+    B = int(lens.shape[0])
+    H = int(tok.shape[1])
+    if B == 0:
+        return (torch.empty((0, 0, H), dtype=out_dtype, device=tok.device),
+                torch.empty((0, 1, 1, 0), dtype=out_dtype, device=tok.device))
+    S = int(lens.max())
+    offsets = np.zeros(B, dtype=np.int64)
+    np.cumsum(lens[:-1], out=offsets[1:])
+
+    def where(code):
+        b, s = divmod(code >> 1, S)
+        src = token_type_ids if code & 1 else input_ids
+        return _bert_embed_bad(
+            name, code & 1, f" of sequence {b}, position {s}",
+            int(src[int(offsets[b]) + s]), type_vocab if code & 1 else vocab)
+
+    if tok.is_cuda:
+        table = torch.empty((B, 2), dtype=torch.int32, pin_memory=True)
+        t = table.numpy()
+        t[:, 0] = offsets
+        t[:, 1] = lens
+        # pinned source: the copy is queued on the current stream and the
+        # caching host allocator keeps the buffer until it has completed
+        table_dev = table.to(tok.device, non_blocking=True)
+        hidden, add_mask, code = require_native().bert_embed(
+            input_ids, table_dev, B, S, None, token_type_ids, tok, pos, typ,
+            gamma, beta, float(eps), pad_id, out_dtype, True)
+        if code >= 0:
+            raise where(code)
+        return hidden, add_mask
+    keep = torch.arange(S)[None, :] < torch.from_numpy(lens)[:, None]
+    ids = torch.full((B, S), pad_id, dtype=input_ids.dtype)
+    ids[keep] = input_ids
+    types = None
+    if token_type_ids is not None:
+        types = torch.zeros((B, S), dtype=input_ids.dtype)
+        types[keep] = token_type_ids
+    bad = _bert_embed_first_bad(ids, types, vocab, type_vocab)
+    if bad is not None:
+        raise where(bad[1] * 2 + bad[0])
+    return bert_embed(ids, tok, pos, typ, gamma, beta, eps, keep, types,
+                      out_dtype)
+
+
 def masked_mean_pool(hidden, mask=None, normalize=False):
     """Fused masked mean-pool head: ``[B,S,H]`` hidden state (f32, bf16 or
     f16, contiguous) -> fp32 ``[B,H]``, one vector per sequence.

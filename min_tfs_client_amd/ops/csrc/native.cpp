@@ -93,6 +93,14 @@ at::Tensor u8_ragged_resize_patch_embed(
     const c10::optional<at::Tensor>& pos,
     const c10::optional<at::Tensor>& cls, at::ScalarType out_dtype,
     int64_t tile);
+// implemented in bert_embed.hip
+std::tuple<at::Tensor, c10::optional<at::Tensor>, int64_t> bert_embed(
+    const at::Tensor& ids, const c10::optional<at::Tensor>& table, int64_t B,
+    int64_t S, const c10::optional<at::Tensor>& mask,
+    const c10::optional<at::Tensor>& types, const at::Tensor& tok,
+    const at::Tensor& pos, const at::Tensor& typ, const at::Tensor& gamma,
+    const at::Tensor& beta, double eps, int64_t pad_id,
+    at::ScalarType out_dtype, bool check);
 at::Tensor dequantize_q8(const at::Tensor& in, double scale, double zp);
 void copy_device_to_host_ptr(const at::Tensor& src, void* dst, size_t n,
                              int mode);
@@ -746,6 +754,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("table"), py::arg("crop_h"), py::arg("crop_w"), py::arg("wk"),
         py::arg("bias"), py::arg("patch"), py::arg("pos"), py::arg("cls"),
         py::arg("out_dtype"), py::arg("tile") = 0);
+  m.def("bert_embed", &mi355x::bert_embed, py::arg("ids"), py::arg("table"),
+        py::arg("batch"), py::arg("seq"), py::arg("mask"), py::arg("types"),
+        py::arg("tok"), py::arg("pos"), py::arg("typ"), py::arg("gamma"),
+        py::arg("beta"), py::arg("eps"), py::arg("pad_id"),
+        py::arg("out_dtype"), py::arg("check") = true);
   m.def("quantize_q8", &mi355x::quantize_q8, py::arg("input"),
         py::arg("scale"), py::arg("zero_point") = 0.0);
   m.def("dequantize_q8", &mi355x::dequantize_q8, py::arg("input"),

@@ -622,3 +622,22 @@ def pack_ragged_images(images):
     if not arrays:
         return np.zeros((0,), dtype=np.uint8), shapes
     return np.concatenate([a.reshape(-1) for a in arrays]), shapes
+
+
+def pack_ragged_tokens(sequences):
+    """Client side of the ragged token layout (``bert_servable``'s
+    ``"ids_ragged"``): a list of id lists -> ``(input_ids,
+    sequence_lengths)``, the int32 ``[total]`` ids back to back and the int32
+    ``[B]`` lengths. Every sequence has at least one id. Numpy only."""
+    arrays = []
+    for i, seq in enumerate(sequences):
+        arr = np.asarray(seq)
+        if arr.ndim != 1 or arr.size == 0 or arr.dtype.kind not in "iu":
+            raise ValueError(
+                f"sequence {i} must be a non-empty 1-D list of integer ids, "
+                f"got dtype {arr.dtype} shape {list(arr.shape)}")
+        arrays.append(arr.astype(np.int32))
+    lengths = np.array([a.size for a in arrays], dtype=np.int32)
+    if not arrays:
+        return np.zeros((0,), dtype=np.int32), lengths
+    return np.concatenate(arrays), lengths

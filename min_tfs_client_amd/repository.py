@@ -32,7 +32,13 @@ On-disk version-directory formats understood by the default loader:
                                "topk"; bert_base: "hidden" or
                                "sentence_embedding"), "top_k" (resnet50,
                                with "topk": 1..64 classes per image) and
-                               "normalize_embedding" (bert_base); vit_b16
+                               "normalize_embedding" (bert_base);
+                               bert_base takes "input_format" too ("ids",
+                               "ids_fused": ids, mask and optional
+                               "token_type_ids" into the fused embedding
+                               kernel, or "ids_ragged": unpadded ids plus
+                               "sequence_lengths" into the same kernel);
+                               vit_b16
                                takes "input_format" ("float_nchw",
                                "uint8_nhwc": raw pixels into the fused
                                patch-embedding kernel, "uint8_nhwc_resize":
@@ -200,7 +206,8 @@ def default_loader(name: str, version_dir: str,
         elif family == "bert_base":
             from .models import bert_servable
             modes = {k: cfg[k]
-                     for k in ("output_format", "normalize_embedding")
+                     for k in ("input_format", "output_format",
+                               "normalize_embedding")
                      if k in cfg}
             servable = bert_servable(device, **modes)
         elif family == "vit_b16":

@@ -82,6 +82,12 @@ class Servable:
     alias and the others are dropped before ``fn``. A request with some but
     not all of them raises ``ValueError``.
 
+    ``signature["optional_inputs"]`` lists declared input aliases that a
+    request may leave out; every other declared input is required. The
+    metadata answers (GetModelMetadata, REST) list such an input like any
+    other: TensorInfo has no field for "optional", so it is documented with
+    the servable, not discoverable on the wire.
+
     ``postprocess`` is the output-side counterpart: an optional callable
     ``{alias: tensor} -> {alias: tensor}`` applied to the whole result of
     ``fn`` (see ``postprocess.py``); what it returns is the response, so
@@ -315,8 +321,10 @@ def validate_inputs_against_signature(servable, inputs) -> Optional[str]:
     sig_inputs = (servable.signature or {}).get("inputs")
     if not sig_inputs:
         return None
-    req = set(inputs)
-    sig = set(sig_inputs)
+    # signature["optional_inputs"]: declared aliases a request may omit
+    optional = set(servable.signature.get("optional_inputs", ()))
+    req = set(inputs) - optional
+    sig = set(sig_inputs) - optional
     if len(req) != len(sig):
         extra = sorted(req - sig)
         missing = sorted(sig - req)
