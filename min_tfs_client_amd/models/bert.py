@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import math
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -35,8 +36,19 @@ class BertLayer(nn.Module):
         self.heads = cfg.heads
         self.head_dim = h // cfg.heads
 
-    def forward(self, x, attn_mask):
+    def forward(self, x, attn_mask, lengths=None):
+        """``lengths`` (int32 (B) on x's device): every mask is the prefix
+        given by its length, and attention runs in the fused length-masked
+        kernel on the projection as stored, with no transposed views, no
+        mask and no copy of the result (``attn_mask`` is not read). Query
+        rows at and past a length are zeros there."""
         B, S, H = x.shape
+        if lengths is not None:
+            from .. import ops
+            attn = ops.masked_self_attention(self.qkv(x), lengths, self.heads)
+            x = self.ln1(x + self.attn_out(attn))
+            return self.ln2(
+                x + self.ff2(torch.nn.functional.gelu(self.ff1(x))))
         qkv = self.qkv(x).view(B, S, 3, self.heads, self.head_dim)
         q, k, v = qkv.unbind(2)  # each B,S,heads,hd
         q = q.transpose(1, 2)
@@ -87,10 +99,12 @@ class BertEncoder(nn.Module):
         m = attention_mask[:, None, None, :].to(dtype)
         return (1.0 - m) * torch.finfo(dtype).min
 
-    def forward_embedded(self, x, mask):
-        """The encoder blocks and the pooler on an embedded input."""
+    def forward_embedded(self, x, mask, lengths=None):
+        """The encoder blocks and the pooler on an embedded input. With
+        ``lengths`` every block runs the fused length-masked attention (see
+        ``BertLayer.forward``); all blocks share the one tensor."""
         for blk in self.blocks:
-            x = blk(x, mask)
+            x = blk(x, mask, lengths)
         pooled = torch.tanh(self.pooler(x[:, 0]))
         return x, pooled
 
@@ -107,7 +121,8 @@ def bert_base() -> BertEncoder:
 def bert_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
                   output_format: str = "hidden",
                   normalize_embedding: bool = True,
-                  input_format: str = "ids", config: BertConfig = None):
+                  input_format: str = "ids", config: BertConfig = None,
+                  attention: str = "sdpa"):
     """BERT-base Servable: inputs "input_ids"/"attention_mask" int32.
 
     ``input_format="ids"`` (default): the encoder input is built by the
@@ -141,6 +156,23 @@ def bert_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
     ``config``: a ``BertConfig`` to build instead of BERT-base (tests serve a
     one-layer model).
 
+    ``attention="sdpa"`` (default): every block runs
+    ``scaled_dot_product_attention`` over the full S x S square with the
+    additive mask. ``attention="fused"``: every block runs
+    ``ops.masked_self_attention``, the length-masked MFMA kernel, on the qkv
+    projection as stored; key and query tiles that are wholly padding are
+    never touched. It needs ``input_format="ids_ragged"`` (the only mode with
+    lengths: a general mask is not a prefix) and a bfloat16 or float16
+    ``dtype`` with 64-wide heads; anything else is a ``ValueError`` here. The
+    request's "sequence_lengths", already validated on the host by the
+    embedding, goes to the device once per request (pinned int32,
+    non-blocking copy) and all blocks share it. Kept positions and
+    "pooled_output" follow the default mode within bf16 / f16 noise;
+    "last_hidden_state" at PADDED positions is finite and deterministic but
+    differs from the default mode, because attention rows there are zeros
+    instead of an average over the kept keys. "sentence_embedding" pools
+    kept positions only and follows the default mode.
+
     ``output_format="hidden"`` (default): outputs "last_hidden_state"
     (B,S,768) + "pooled_output" (B,768), both DT_FLOAT.
     ``output_format="sentence_embedding"``: the only output is
@@ -161,13 +193,31 @@ def bert_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
         raise ValueError(
             f"input_format must be 'ids', 'ids_fused' or 'ids_ragged', got "
             f"{input_format!r}")
+    if attention not in ("sdpa", "fused"):
+        raise ValueError(
+            f"attention must be 'sdpa' or 'fused', got {attention!r}")
+    cfg = BertConfig() if config is None else config
+    fused_attention = attention == "fused"
+    if fused_attention:
+        if input_format != "ids_ragged":
+            raise ValueError(
+                "attention='fused' needs input_format='ids_ragged' (the "
+                "only mode whose masks are prefixes given by lengths), got "
+                f"{input_format!r}")
+        if dtype not in (torch.bfloat16, torch.float16):
+            raise ValueError(
+                "attention='fused' needs dtype bfloat16 or float16, got "
+                f"{dtype}")
+        if cfg.hidden != cfg.heads * ops.ATTENTION_HEAD_DIM:
+            raise ValueError(
+                f"attention='fused' needs {ops.ATTENTION_HEAD_DIM}-wide "
+                f"heads, got hidden {cfg.hidden} over {cfg.heads} heads")
     embed = output_format == "sentence_embedding"
     normalize_embedding = bool(normalize_embedding)
     fused = input_format == "ids_fused"
     ragged = input_format == "ids_ragged"
 
     torch.manual_seed(seed)
-    cfg = BertConfig() if config is None else config
     model = BertEncoder(cfg).to(device=device, dtype=dtype).eval()
 
     def on_device(value):
@@ -176,6 +226,18 @@ def bert_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
         if not isinstance(value, torch.Tensor):
             value = torch.as_tensor(value)
         return value.to(device=device)
+
+    def device_lengths(lengths):
+        """The request's lengths as int32 on the model's device: from a
+        pinned buffer on the current stream, no synchronization."""
+        if not isinstance(lengths, torch.Tensor):
+            lengths = torch.as_tensor(np.asarray(lengths))
+        if lengths.is_cuda or torch.device(device).type != "cuda":
+            return lengths.to(device=device, dtype=torch.int32)
+        host = torch.empty(lengths.shape, dtype=torch.int32, pin_memory=True)
+        host.copy_(lengths)
+        # the caching host allocator keeps the buffer until the copy is done
+        return host.to(device, non_blocking=True)
 
     def fused_embed(inputs):
         """(encoder input, additive mask, pooling mask) from the fused
@@ -202,7 +264,9 @@ def bert_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
     def fn(inputs):
         if fused or ragged:
             x, add_mask, mask = fused_embed(inputs)
-            hidden, pooled = s.module.forward_embedded(x, add_mask)
+            lengths = device_lengths(inputs["sequence_lengths"]) \
+                if fused_attention else None
+            hidden, pooled = s.module.forward_embedded(x, add_mask, lengths)
         else:
             ids = on_device(inputs["input_ids"])
             mask = on_device(inputs.get("attention_mask"))

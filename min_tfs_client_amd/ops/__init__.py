@@ -8,6 +8,7 @@ to eager PyTorch, so a passing GPU test means the HIP path actually ran.
 from __future__ import annotations
 
 import functools
+import math
 import operator
 from typing import Optional
 
@@ -1598,6 +1599,97 @@ def masked_mean_pool(hidden, mask=None, normalize=False):
     if normalize:
         y = y / y.norm(dim=1, keepdim=True).clamp(min=1e-12)
     return y.contiguous()
+
+
+ATTENTION_HEAD_DIM = 64
+
+
+def masked_self_attention(qkv, lengths, heads, scale=None):
+    """Fused length-masked multi-head self-attention: the ``[B,S,3*H]`` qkv
+    projection (bf16 or f16, contiguous, last axis ordered ``(3, heads,
+    head_dim)`` as ``BertLayer.qkv`` emits it, ``head_dim == 64``) ->
+    ``[B,S,H]`` of the same dtype, written in that layout directly.
+
+    For sequence ``b`` with ``L = clamp(lengths[b], 0, S)``::
+
+        out[b,s,h*64:(h+1)*64] = softmax_{j<L}((q_s . k_j) * scale) @ v_j   s < L
+        out[b,s,:]             = +0.0                                  s >= L
+
+    ``lengths`` is int32 ``[B]`` on the device of ``qkv``; ``None`` means
+    every sequence is ``S`` long. ``scale`` defaults to ``1/sqrt(head_dim)``.
+    Keys, values and queries at or past ``L`` are selected out, never
+    multiplied in: a NaN or Inf stored there does not reach a kept output
+    (the rule of :func:`masked_mean_pool`). Products and sums are fp32, the
+    softmax is fp32, P is rounded once to the input dtype for ``P @ V`` and
+    the result once at the store. Reruns are bit-identical and a sequence's
+    output does not depend on its batch neighbours.
+
+    Device tensors run the gfx950 MFMA kernel only (no eager fallback, no
+    host synchronization: the lengths are clamped on the device); CPU tensors
+    run an eager fp32 expression with the same semantics, so CPU-only servers
+    work too. Invalid arguments raise ``ValueError`` on both paths, before
+    any launch. ``B == 0`` or ``S == 0`` returns an empty tensor."""
+    name = "masked_self_attention"
+    if not isinstance(qkv, torch.Tensor):
+        raise ValueError(f"{name} expects a torch tensor")
+    if qkv.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(
+            f"{name} expects bfloat16 or float16 qkv, got {qkv.dtype}")
+    if qkv.dim() != 3:
+        raise ValueError(f"{name} expects [B,S,3*H], got rank {qkv.dim()}")
+    if not qkv.is_contiguous():
+        raise ValueError(f"{name} expects a contiguous tensor")
+    try:
+        if isinstance(heads, bool):
+            raise TypeError
+        heads = operator.index(heads)
+    except TypeError:
+        raise ValueError(f"heads must be an integer, got {heads!r}") from None
+    B, S, H3 = (int(d) for d in qkv.shape)
+    if heads < 1 or H3 % (3 * heads):
+        raise ValueError(
+            f"{name}: the last axis ({H3}) must be 3 * heads ({heads}) * "
+            "head_dim")
+    head_dim = H3 // (3 * heads)
+    if head_dim != ATTENTION_HEAD_DIM:
+        raise ValueError(
+            f"{name}: head_dim must be {ATTENTION_HEAD_DIM}, got {head_dim}")
+    if qkv.data_ptr() % 16:
+        raise ValueError(f"{name}: qkv must be 16-byte aligned")
+    if scale is None:
+        scale = 1.0 / math.sqrt(head_dim)
+    scale = float(scale)
+    if not math.isfinite(scale):
+        raise ValueError(f"{name}: scale must be finite, got {scale}")
+    if lengths is not None:
+        if not isinstance(lengths, torch.Tensor) or \
+                lengths.dtype != torch.int32:
+            raise ValueError(f"{name}: lengths must be an int32 tensor")
+        if tuple(lengths.shape) != (B,):
+            raise ValueError(
+                f"{name}: lengths must have shape {[B]}, got "
+                f"{list(lengths.shape)}")
+        if lengths.device != qkv.device:
+            raise ValueError(
+                f"{name}: lengths is on {lengths.device} but qkv is on "
+                f"{qkv.device}")
+        lengths = lengths.contiguous()
+    if qkv.is_cuda:
+        return require_native().masked_self_attention(qkv, lengths, heads,
+                                                      scale)
+    H = H3 // 3
+    q, k, v = (t.transpose(1, 2) for t in
+               qkv.float().view(B, S, 3, heads, head_dim).unbind(2))
+    n = torch.full((B,), S) if lengths is None else lengths.clamp(0, S)
+    keep = torch.arange(S)[None, :] < n[:, None]             # [B,S]
+    rows, cols = keep[:, None, :, None], keep[:, None, None, :]
+    zero = torch.zeros(())
+    q, k, v = (torch.where(rows, t, zero) for t in (q, k, v))
+    scores = torch.where(cols, (q @ k.transpose(2, 3)) * scale,
+                         torch.full((), float("-inf")))
+    # a sequence with nothing kept: softmax of all -inf is NaN, selected out
+    p = torch.where(rows & cols, torch.softmax(scores, -1), zero)
+    return (p @ v).transpose(1, 2).reshape(B, S, H).to(qkv.dtype)
 
 
 SOFTMAX_TOPK_MAX_K = 64

@@ -37,7 +37,12 @@ On-disk version-directory formats understood by the default loader:
                                "ids_fused": ids, mask and optional
                                "token_type_ids" into the fused embedding
                                kernel, or "ids_ragged": unpadded ids plus
-                               "sequence_lengths" into the same kernel);
+                               "sequence_lengths" into the same kernel),
+                               "dtype" ("float32", the default, "bfloat16"
+                               or "float16") and "attention" ("sdpa", or
+                               "fused": the length-masked MFMA attention
+                               kernel, with "ids_ragged" and a 16-bit
+                               "dtype");
                                vit_b16
                                takes "input_format" ("float_nchw",
                                "uint8_nhwc": raw pixels into the fused
@@ -207,8 +212,18 @@ def default_loader(name: str, version_dir: str,
             from .models import bert_servable
             modes = {k: cfg[k]
                      for k in ("input_format", "output_format",
-                               "normalize_embedding")
+                               "normalize_embedding", "attention")
                      if k in cfg}
+            if "dtype" in cfg:
+                import torch
+                dtypes = {"float32": torch.float32,
+                          "bfloat16": torch.bfloat16,
+                          "float16": torch.float16}
+                if cfg["dtype"] not in dtypes:
+                    raise ValueError(
+                        f"model.json of {name}: dtype must be one of "
+                        f"{sorted(dtypes)}, got {cfg['dtype']!r}")
+                modes["dtype"] = dtypes[cfg["dtype"]]
             servable = bert_servable(device, **modes)
         elif family == "vit_b16":
             from .models import vit_b16_servable

@@ -28,6 +28,7 @@ ext = CUDAExtension(
         os.path.join(_CSRC, "pack_kernels.hip"),
         os.path.join(_CSRC, "patch_embed.hip"),
         os.path.join(_CSRC, "bert_embed.hip"),
+        os.path.join(_CSRC, "attention.hip"),
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
