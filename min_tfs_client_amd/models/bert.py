@@ -36,19 +36,25 @@ class BertLayer(nn.Module):
         self.heads = cfg.heads
         self.head_dim = h // cfg.heads
 
-    def forward(self, x, attn_mask, lengths=None):
+    def forward(self, x, attn_mask, lengths=None, tiles=None):
         """``lengths`` (int32 (B) on x's device): every mask is the prefix
         given by its length, and attention runs in the fused length-masked
         kernel on the projection as stored, with no transposed views, no
         mask and no copy of the result (``attn_mask`` is not read). Query
-        rows at and past a length are zeros there."""
-        B, S, H = x.shape
-        if lengths is not None:
+        rows at and past a length are zeros there.
+
+        ``tiles`` (``ops.attention_tiles`` on x's device): ``x`` is packed,
+        (T,H) with the sequences back to back, and the projection goes to
+        the packed form of the same kernel; every other layer of the block
+        is row-wise and runs on the T rows as it is."""
+        if lengths is not None or tiles is not None:
             from .. import ops
-            attn = ops.masked_self_attention(self.qkv(x), lengths, self.heads)
+            attn = ops.masked_self_attention(self.qkv(x), lengths, self.heads,
+                                             tiles=tiles)
             x = self.ln1(x + self.attn_out(attn))
             return self.ln2(
                 x + self.ff2(torch.nn.functional.gelu(self.ff1(x))))
+        B, S, H = x.shape
         qkv = self.qkv(x).view(B, S, 3, self.heads, self.head_dim)
         q, k, v = qkv.unbind(2)  # each B,S,heads,hd
         q = q.transpose(1, 2)
@@ -99,13 +105,18 @@ class BertEncoder(nn.Module):
         m = attention_mask[:, None, None, :].to(dtype)
         return (1.0 - m) * torch.finfo(dtype).min
 
-    def forward_embedded(self, x, mask, lengths=None):
+    def forward_embedded(self, x, mask, lengths=None, tiles=None,
+                         first_rows=None):
         """The encoder blocks and the pooler on an embedded input. With
         ``lengths`` every block runs the fused length-masked attention (see
-        ``BertLayer.forward``); all blocks share the one tensor."""
+        ``BertLayer.forward``); all blocks share the one tensor. With
+        ``tiles`` the input is packed (T,H) and stays packed through every
+        block; ``first_rows`` (int64 (B)) is the first row of each sequence,
+        which the pooler reads."""
         for blk in self.blocks:
-            x = blk(x, mask, lengths)
-        pooled = torch.tanh(self.pooler(x[:, 0]))
+            x = blk(x, mask, lengths, tiles)
+        first = x[:, 0] if tiles is None else x.index_select(0, first_rows)
+        pooled = torch.tanh(self.pooler(first))
         return x, pooled
 
     def forward(self, input_ids, attention_mask=None):
@@ -173,6 +184,20 @@ def bert_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
     instead of an average over the kept keys. "sentence_embedding" pools
     kept positions only and follows the default mode.
 
+    ``attention="packed"``: the same constraints as ``"fused"``, and the
+    batch stays packed from the ids to the last block: the embedding kernel
+    writes (total,H) (``ops.bert_embed_ragged(packed=True)``), every block
+    runs its GEMMs, LayerNorms and GELU on those ``total`` rows instead of
+    ``B * S`` and its attention in the packed form of the kernel. Per
+    request the lengths are read once on the host, which builds the
+    embedding's table, the tile table (``ops.attention_tiles``) and two
+    index vectors (the first row of each sequence, and ``b * S + s`` of each
+    packed row), all shipped from pinned memory without a synchronization.
+    After the last block the rows are scattered into zeros once
+    (``index_copy_``): "last_hidden_state" has S = the longest length and
+    is exactly +0.0 at padded positions; kept positions, "pooled_output"
+    and "sentence_embedding" follow the default mode as ``"fused"`` does.
+
     ``output_format="hidden"`` (default): outputs "last_hidden_state"
     (B,S,768) + "pooled_output" (B,768), both DT_FLOAT.
     ``output_format="sentence_embedding"``: the only output is
@@ -193,24 +218,26 @@ def bert_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
         raise ValueError(
             f"input_format must be 'ids', 'ids_fused' or 'ids_ragged', got "
             f"{input_format!r}")
-    if attention not in ("sdpa", "fused"):
+    if attention not in ("sdpa", "fused", "packed"):
         raise ValueError(
-            f"attention must be 'sdpa' or 'fused', got {attention!r}")
+            f"attention must be 'sdpa' or 'fused' or 'packed', got "
+            f"{attention!r}")
     cfg = BertConfig() if config is None else config
     fused_attention = attention == "fused"
-    if fused_attention:
+    packed_attention = attention == "packed"
+    if fused_attention or packed_attention:
         if input_format != "ids_ragged":
             raise ValueError(
-                "attention='fused' needs input_format='ids_ragged' (the "
-                "only mode whose masks are prefixes given by lengths), got "
-                f"{input_format!r}")
+                f"attention={attention!r} needs input_format='ids_ragged' "
+                "(the only mode whose masks are prefixes given by lengths), "
+                f"got {input_format!r}")
         if dtype not in (torch.bfloat16, torch.float16):
             raise ValueError(
-                "attention='fused' needs dtype bfloat16 or float16, got "
-                f"{dtype}")
+                f"attention={attention!r} needs dtype bfloat16 or float16, "
+                f"got {dtype}")
         if cfg.hidden != cfg.heads * ops.ATTENTION_HEAD_DIM:
             raise ValueError(
-                f"attention='fused' needs {ops.ATTENTION_HEAD_DIM}-wide "
+                f"attention={attention!r} needs {ops.ATTENTION_HEAD_DIM}-wide "
                 f"heads, got hidden {cfg.hidden} over {cfg.heads} heads")
     embed = output_format == "sentence_embedding"
     normalize_embedding = bool(normalize_embedding)
@@ -260,9 +287,52 @@ def bert_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
             out_dtype=out_dtype)
         return x, add_mask, mask
 
+    def pinned_to_device(host):
+        """A host tensor on the model's device: through a pinned buffer on
+        the current stream, no synchronization."""
+        if torch.device(device).type != "cuda":
+            return host
+        pinned = torch.empty(host.shape, dtype=host.dtype, pin_memory=True)
+        pinned.copy_(host)
+        # the caching host allocator keeps the buffer until the copy is done
+        return pinned.to(device, non_blocking=True)
+
+    def packed_forward(inputs):
+        """(hidden (B,S,H) with +0.0 at padded positions, pooled, pooling
+        mask) of a ragged request that stays packed through the encoder."""
+        m = s.module
+        lengths = inputs["sequence_lengths"]
+        # validates the lengths against the ids and max_pos, on the host
+        x = ops.bert_embed_ragged(
+            on_device(inputs["input_ids"]), lengths, m.tok.weight,
+            m.pos.weight, m.typ.weight, m.ln.weight, m.ln.bias, m.ln.eps,
+            token_type_ids=on_device(inputs.get("token_type_ids")),
+            out_dtype=m.tok.weight.dtype, packed=True)
+        if isinstance(lengths, torch.Tensor):
+            lengths = lengths.cpu().numpy()
+        lens = np.asarray(lengths).astype(np.int64)
+        B, S = len(lens), int(lens.max()) if len(lens) else 0
+        offsets = np.cumsum(lens) - lens
+        seq = np.repeat(np.arange(B), lens)
+        # first row of each sequence, then b * S + s of each packed row
+        index = pinned_to_device(torch.from_numpy(np.concatenate(
+            (offsets, seq * S + (np.arange(len(seq)) - offsets[seq])))))
+        tiles = ops.attention_tiles(lens, device)
+        x, pooled = m.forward_embedded(x, None, tiles=tiles,
+                                       first_rows=index[:B])
+        hidden = x.new_zeros((B * S, x.shape[1])).index_copy_(
+            0, index[B:], x).view(B, S, x.shape[1])
+        mask = None
+        if embed:
+            mask = torch.arange(S, device=device)[None, :] < \
+                pinned_to_device(torch.from_numpy(lens))[:, None]
+        return hidden, pooled, mask
+
     @torch.no_grad()
     def fn(inputs):
-        if fused or ragged:
+        if packed_attention:
+            hidden, pooled, mask = packed_forward(inputs)
+        elif fused or ragged:
             x, add_mask, mask = fused_embed(inputs)
             lengths = device_lengths(inputs["sequence_lengths"]) \
                 if fused_attention else None

@@ -1444,7 +1444,8 @@ def _bert_ragged_lengths(name, lengths, total, max_pos):
 
 
 def bert_embed_ragged(input_ids, lengths, tok, pos, typ, gamma, beta, eps,
-                      token_type_ids=None, pad_id=0, out_dtype=None):
+                      token_type_ids=None, pad_id=0, out_dtype=None,
+                      packed=False):
     """:func:`bert_embed` of a ragged batch: B sequences of B lengths, their
     ids back to back in ``input_ids [total]`` with no padding, go to
     ``(hidden [B,S,H], additive_mask [B,1,1,S])`` with ``S = max(lengths)``,
@@ -1463,6 +1464,11 @@ def bert_embed_ragged(input_ids, lengths, tok, pos, typ, gamma, beta, eps,
         mask = arange(S)[None] < lengths[:, None]
         out == bert_embed(ids, ..., attention_mask=mask,
                           token_type_ids=<padded with 0>)
+
+    ``packed=True`` returns ``hidden [total,H]`` alone, the kept rows back to
+    back in the order of ``input_ids`` and no mask: ``hidden_padded[mask]`` of
+    the default call, bit for bit. The kernel skips the padded rows instead
+    of computing them.
 
     CPU tensors run exactly this. Device tensors run the gfx950 kernel only
     (no eager fallback): the host builds an int32 ``(offset, length)`` table
@@ -1492,6 +1498,8 @@ def bert_embed_ragged(input_ids, lengths, tok, pos, typ, gamma, beta, eps,
     lens = _bert_ragged_lengths(name, lengths, total, int(pos.shape[0]))
     B = int(lens.shape[0])
     H = int(tok.shape[1])
+    if B == 0 and packed:
+        return torch.empty((0, H), dtype=out_dtype, device=tok.device)
     if B == 0:
         return (torch.empty((0, 0, H), dtype=out_dtype, device=tok.device),
                 torch.empty((0, 1, 1, 0), dtype=out_dtype, device=tok.device))
@@ -1516,10 +1524,10 @@ def bert_embed_ragged(input_ids, lengths, tok, pos, typ, gamma, beta, eps,
         table_dev = table.to(tok.device, non_blocking=True)
         hidden, add_mask, code = require_native().bert_embed(
             input_ids, table_dev, B, S, None, token_type_ids, tok, pos, typ,
-            gamma, beta, float(eps), pad_id, out_dtype, True)
+            gamma, beta, float(eps), pad_id, out_dtype, True, bool(packed))
         if code >= 0:
             raise where(code)
-        return hidden, add_mask
+        return hidden if packed else (hidden, add_mask)
     keep = torch.arange(S)[None, :] < torch.from_numpy(lens)[:, None]
     ids = torch.full((B, S), pad_id, dtype=input_ids.dtype)
     ids[keep] = input_ids
@@ -1530,8 +1538,9 @@ def bert_embed_ragged(input_ids, lengths, tok, pos, typ, gamma, beta, eps,
     bad = _bert_embed_first_bad(ids, types, vocab, type_vocab)
     if bad is not None:
         raise where(bad[1] * 2 + bad[0])
-    return bert_embed(ids, tok, pos, typ, gamma, beta, eps, keep, types,
-                      out_dtype)
+    hidden, add_mask = bert_embed(ids, tok, pos, typ, gamma, beta, eps, keep,
+                                  types, out_dtype)
+    return hidden[keep] if packed else (hidden, add_mask)
 
 
 def masked_mean_pool(hidden, mask=None, normalize=False):
@@ -1604,7 +1613,70 @@ def masked_mean_pool(hidden, mask=None, normalize=False):
 ATTENTION_HEAD_DIM = 64
 
 
-def masked_self_attention(qkv, lengths, heads, scale=None):
+def attention_tiles(lengths, device=None):
+    """The tile table of the packed form of :func:`masked_self_attention`:
+    int32 ``[ntiles,4]``, one row ``(row0, L, q0, seq)`` per 64-row query
+    tile of every sequence, ``ntiles = sum(ceil(len/64))``. ``row0`` is the
+    sequence's first row in the packed ``[total, ...]`` tensor (sequences
+    back to back in the order of ``lengths``), ``L`` its length, ``q0`` the
+    tile's first query (a multiple of 64 below ``L``) and ``seq`` its index
+    in ``lengths``. Every packed row is covered exactly once.
+
+    Rows are longest sequence first (a stable sort: equal lengths keep the
+    order of ``lengths``), tiles ascending inside a sequence. A workgroup's
+    cost grows with ``L`` and the table's order is the dispatch order, so the
+    long sequences start first and do not form the tail; the kernel's file
+    header has the measurement behind that order.
+
+    ``lengths`` is read on the **host**: a list, a numpy array or a CPU
+    tensor of integers, each at least 1 (a device tensor costs a small
+    synchronizing D2H copy). With a device the table is built in a pinned
+    buffer and copied on the current stream without synchronization;
+    ``device=None`` returns the CPU tensor. An empty list gives ``[0,4]``."""
+    import numpy as np
+
+    name = "attention_tiles"
+    if isinstance(lengths, torch.Tensor):
+        lengths = lengths.cpu().numpy()    # device tensor: synchronizing D2H
+    try:
+        arr = np.asarray(lengths)
+    except (TypeError, ValueError):
+        arr = None
+    if arr is not None and arr.size == 0 and arr.ndim == 1:
+        arr = np.zeros((0,), dtype=np.int64)
+    if arr is None or arr.dtype.kind not in "iu" or arr.ndim != 1:
+        raise ValueError(
+            f"{name}: lengths must be integer [B], got {lengths!r}")
+    arr = arr.astype(np.int64)
+    bad = _first_bad(arr < 1)
+    if bad is not None:
+        raise ValueError(
+            f"{name}: sequence {bad}: length must be at least 1, got "
+            f"{int(arr[bad])}")
+    if int(arr.sum()) >= 1 << 30:
+        raise ValueError(f"{name}: the lengths must sum to less than 2^30")
+    per_seq = (arr + 63) // 64
+    n = int(per_seq.sum())
+    to_device = device is not None and torch.device(device).type == "cuda"
+    table = torch.empty((n, 4), dtype=torch.int32,
+                        pin_memory=n > 0 and to_device)
+    t = table.numpy()
+    order = np.argsort(-arr, kind="stable")
+    counts = per_seq[order]
+    seq = np.repeat(order, counts)
+    t[:, 0] = (np.cumsum(arr) - arr)[seq]
+    t[:, 1] = arr[seq]
+    t[:, 2] = (np.arange(n) - np.repeat(np.cumsum(counts) - counts,
+                                        counts)) * 64
+    t[:, 3] = seq
+    if device is None:
+        return table
+    # pinned source: the copy is queued on the current stream and the
+    # caching host allocator keeps the buffer until it has completed
+    return table.to(device, non_blocking=True)
+
+
+def masked_self_attention(qkv, lengths, heads, scale=None, *, tiles=None):
     """Fused length-masked multi-head self-attention: the ``[B,S,3*H]`` qkv
     projection (bf16 or f16, contiguous, last axis ordered ``(3, heads,
     head_dim)`` as ``BertLayer.qkv`` emits it, ``head_dim == 64``) ->
@@ -1624,19 +1696,41 @@ def masked_self_attention(qkv, lengths, heads, scale=None):
     the result once at the store. Reruns are bit-identical and a sequence's
     output does not depend on its batch neighbours.
 
+    Packed (varlen) form: a rank-2 ``qkv [T,3*H]`` holds the sequences back
+    to back with no padding and the result is ``[T,H]``. ``tiles`` (keyword
+    only, required, int32 ``[n,4]`` contiguous on the device of ``qkv``, from
+    :func:`attention_tiles`) says where each sequence lies and ``lengths``
+    must be ``None``. For every sequence ``(row0, L)`` of the table, bit for
+    bit on both paths::
+
+        out[row0:row0+L] == masked_self_attention(
+                                qkv[row0:row0+L][None], None, heads, scale)[0]
+
+    No row of a neighbouring sequence is loaded and no row past ``row0 + L``
+    is stored. The kernel launches exactly ``n * heads`` workgroups. A table
+    cannot cause a fault: ``row0`` is clamped to ``0..T``, ``L`` to ``0..T -
+    row0`` and ``q0`` to ``>= 0`` on the device, and an entry with ``q0 >=
+    L`` does nothing. Rows of ``out`` that no entry covers are unspecified.
+
     Device tensors run the gfx950 MFMA kernel only (no eager fallback, no
     host synchronization: the lengths are clamped on the device); CPU tensors
-    run an eager fp32 expression with the same semantics, so CPU-only servers
+    run an eager fp32 expression with the same semantics (the packed form:
+    exactly the loop above over the table's entries), so CPU-only servers
     work too. Invalid arguments raise ``ValueError`` on both paths, before
-    any launch. ``B == 0`` or ``S == 0`` returns an empty tensor."""
+    any launch: among them a rank other than 2 or 3, a rank-2 ``qkv``
+    without ``tiles`` or with ``lengths``, ``tiles`` with a rank-3 ``qkv``,
+    ``tiles`` of the wrong dtype, shape or device. ``B == 0``, ``S == 0`` or
+    ``T == 0`` returns an empty tensor."""
     name = "masked_self_attention"
     if not isinstance(qkv, torch.Tensor):
         raise ValueError(f"{name} expects a torch tensor")
     if qkv.dtype not in (torch.bfloat16, torch.float16):
         raise ValueError(
             f"{name} expects bfloat16 or float16 qkv, got {qkv.dtype}")
-    if qkv.dim() != 3:
-        raise ValueError(f"{name} expects [B,S,3*H], got rank {qkv.dim()}")
+    if qkv.dim() not in (2, 3):
+        raise ValueError(
+            f"{name} expects [B,S,3*H] or [T,3*H], got rank {qkv.dim()}")
+    packed = qkv.dim() == 2
     if not qkv.is_contiguous():
         raise ValueError(f"{name} expects a contiguous tensor")
     try:
@@ -1645,7 +1739,8 @@ def masked_self_attention(qkv, lengths, heads, scale=None):
         heads = operator.index(heads)
     except TypeError:
         raise ValueError(f"heads must be an integer, got {heads!r}") from None
-    B, S, H3 = (int(d) for d in qkv.shape)
+    S, H3 = (int(d) for d in qkv.shape[-2:])
+    B = 1 if packed else int(qkv.shape[0])
     if heads < 1 or H3 % (3 * heads):
         raise ValueError(
             f"{name}: the last axis ({H3}) must be 3 * heads ({heads}) * "
@@ -1661,6 +1756,36 @@ def masked_self_attention(qkv, lengths, heads, scale=None):
     scale = float(scale)
     if not math.isfinite(scale):
         raise ValueError(f"{name}: scale must be finite, got {scale}")
+    if packed:
+        if tiles is None:
+            raise ValueError(
+                f"{name}: a rank-2 (packed) qkv needs tiles, see "
+                "attention_tiles")
+        if lengths is not None:
+            raise ValueError(
+                f"{name}: tiles and lengths exclude each other: a packed "
+                "qkv takes its lengths from the table")
+        if not isinstance(tiles, torch.Tensor) or tiles.dtype != torch.int32:
+            raise ValueError(
+                f"{name}: tiles must be an int32 tensor, got "
+                f"{getattr(tiles, 'dtype', type(tiles))}")
+        if tiles.dim() != 2 or tiles.shape[1] != 4:
+            raise ValueError(
+                f"{name}: tiles must have shape [n,4], got "
+                f"{list(tiles.shape)}")
+        if tiles.device != qkv.device:
+            raise ValueError(
+                f"{name}: tiles is on {tiles.device} but qkv is on "
+                f"{qkv.device}")
+        if not tiles.is_contiguous():
+            raise ValueError(f"{name}: tiles must be contiguous")
+        if S >= 1 << 30 or tiles.shape[0] * heads >= 1 << 24:
+            raise ValueError(
+                f"{name}: T must be below 2^30 and n * heads below 2^24, "
+                f"got T={S} n={tiles.shape[0]} heads={heads}")
+    elif tiles is not None:
+        raise ValueError(
+            f"{name}: tiles go with a rank-2 (packed) qkv, got rank 3")
     if lengths is not None:
         if not isinstance(lengths, torch.Tensor) or \
                 lengths.dtype != torch.int32:
@@ -1676,8 +1801,25 @@ def masked_self_attention(qkv, lengths, heads, scale=None):
         lengths = lengths.contiguous()
     if qkv.is_cuda:
         return require_native().masked_self_attention(qkv, lengths, heads,
-                                                      scale)
+                                                      scale, tiles)
     H = H3 // 3
+    if packed:
+        # the kernel's walk over the table, clamps included; uncovered rows
+        # are unspecified (zeros here)
+        out = qkv.new_zeros((S, H))
+        done = {}
+        for row0, n, q0, _ in tiles.tolist():
+            row0 = min(max(row0, 0), S)
+            n = min(max(n, 0), S - row0)
+            q0 = max(q0, 0)
+            if q0 >= n:
+                continue
+            if (row0, n) not in done:
+                done[row0, n] = masked_self_attention(
+                    qkv[row0:row0 + n][None], None, heads, scale)[0]
+            q1 = min(q0 + 64, n)
+            out[row0 + q0:row0 + q1] = done[row0, n][q0:q1]
+        return out
     q, k, v = (t.transpose(1, 2) for t in
                qkv.float().view(B, S, 3, heads, head_dim).unbind(2))
     n = torch.full((B,), S) if lengths is None else lengths.clamp(0, S)

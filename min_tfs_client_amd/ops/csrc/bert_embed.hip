@@ -49,6 +49,12 @@
 // row (b,s) takes ids[offset+s] (and types[offset+s]) when s < length, else
 // pad_id (type 0); "kept" is s < length. Dense form: "kept" is mask != 0.
 //
+// Packed output (ragged form only): a row with s >= length is skipped before
+// any load, a kept row is stored at row offset + s of a [total,H] tensor, and
+// there is no mask. The skip is per wave (the row is scalar), the arithmetic
+// of a kept row is untouched, so the result is the kept rows of the padded
+// output bit for bit. The error code stays row * 2 + kind in (b, s) space.
+//
 // Resource usage (hipcc -O3 --offload-arch=gfx950
 // -Rpass-analysis=kernel-resource-usage), scratch is 0 bytes/lane in every
 // of the 78 instantiations and none uses LDS (int32 ids; int64 ids differ by
@@ -96,11 +102,12 @@ struct BertEmbedParams {
   const void* typ;          // [type_vocab, H]
   const void* gamma;        // [H]
   const void* beta;         // [H]
-  void* out;                // OUT [B,S,H]
+  void* out;                // OUT [B,S,H], packed: [total,H]
   void* mask_out;           // OUT [B,S] or null
   int32_t* err;             // error slot or null (no report)
   int64_t pad_id;
   int rows, S, H, vocab, type_vocab, mask_bytes;
+  int packed;               // ragged only: store kept rows at offset + s
   float eps;
 };
 
@@ -217,10 +224,15 @@ void bert_embed_kernel(const BertEmbedParams p) {
        row += step) {
     const int b = row / p.S, s = row - b * p.S;
     int64_t id, t = 0;
+    int64_t out_row = row;
     bool keep = true;
     if (p.table) {
       const int off = p.table[2 * b], len = p.table[2 * b + 1];
       keep = s < len;
+      if (p.packed) {
+        if (!keep) continue;                    // wave-uniform
+        out_row = off + s;
+      }
       id = keep ? int64_t(ids[off + s]) : p.pad_id;
       if (keep && types) t = int64_t(types[off + s]);
     } else {
@@ -277,7 +289,7 @@ void bert_embed_kernel(const BertEmbedParams p) {
     const float var = __fdiv_rn(be_wave_sum(ssd), fH);
     const float rstd = __fdiv_rn(1.0f, sqrtf(var + p.eps));
 
-    OutT* out = static_cast<OutT*>(p.out) + int64_t(row) * p.H;
+    OutT* out = static_cast<OutT*>(p.out) + out_row * p.H;
 #pragma unroll
     for (int i = 0; i < CPL; ++i) {
       const int c = lane + 64 * i;
@@ -383,16 +395,20 @@ void be_give_slot(const at::Tensor& slot) {
 // undefined tensor, error code): the code is -1 for a clean batch, else
 // row*2 + (0: id, 1: type) of the lowest bad row; `check=false` skips the
 // report and the D2H read (the kernel still never indexes with a bad value).
-// Arguments the kernel cannot serve are ValueError.
+// `packed` (ragged form only): hidden is [total,H], the kept rows back to
+// back, and there is no mask; the caller checked that the table's rows tile
+// 0..total. Arguments the kernel cannot serve are ValueError.
 std::tuple<at::Tensor, c10::optional<at::Tensor>, int64_t> bert_embed(
     const at::Tensor& ids, const c10::optional<at::Tensor>& table, int64_t B,
     int64_t S, const c10::optional<at::Tensor>& mask,
     const c10::optional<at::Tensor>& types, const at::Tensor& tok,
     const at::Tensor& pos, const at::Tensor& typ, const at::Tensor& gamma,
     const at::Tensor& beta, double eps, int64_t pad_id,
-    at::ScalarType out_dtype, bool check) {
+    at::ScalarType out_dtype, bool check, bool packed) {
   const char* who = "bert_embed";
   const bool ragged = table.has_value();
+  TORCH_CHECK_VALUE(ragged || !packed, who,
+                    ": packed output needs the ragged form");
   TORCH_CHECK_VALUE(out_dtype == at::kFloat || out_dtype == at::kBFloat16 ||
                     out_dtype == at::kHalf,
                     who, ": out_dtype must be f32, bf16 or f16");
@@ -466,9 +482,11 @@ std::tuple<at::Tensor, c10::optional<at::Tensor>, int64_t> bert_embed(
     mask_bytes = int(mask->element_size());
   }
 
-  auto out = at::empty({B, S, H}, tok.options().dtype(out_dtype));
+  auto out = packed
+                 ? at::empty({ids.size(0), H}, tok.options().dtype(out_dtype))
+                 : at::empty({B, S, H}, tok.options().dtype(out_dtype));
   c10::optional<at::Tensor> mask_out;
-  if (ragged || mask.has_value())
+  if (!packed && (ragged || mask.has_value()))
     mask_out = at::empty({B, 1, 1, S}, out.options());
   at::Tensor slot;
   if (check) slot = be_take_slot(ids);
@@ -494,6 +512,7 @@ std::tuple<at::Tensor, c10::optional<at::Tensor>, int64_t> bert_embed(
   p.vocab = int(tok.size(0));
   p.type_vocab = int(typ.size(0));
   p.mask_bytes = mask_bytes;
+  p.packed = packed ? 1 : 0;
   p.eps = float(eps);
 
   const int groups =

@@ -100,11 +100,12 @@ std::tuple<at::Tensor, c10::optional<at::Tensor>, int64_t> bert_embed(
     const c10::optional<at::Tensor>& types, const at::Tensor& tok,
     const at::Tensor& pos, const at::Tensor& typ, const at::Tensor& gamma,
     const at::Tensor& beta, double eps, int64_t pad_id,
-    at::ScalarType out_dtype, bool check);
+    at::ScalarType out_dtype, bool check, bool packed);
 // implemented in attention.hip
 at::Tensor masked_self_attention(const at::Tensor& qkv,
                                  const c10::optional<at::Tensor>& lengths,
-                                 int64_t heads, double scale);
+                                 int64_t heads, double scale,
+                                 const c10::optional<at::Tensor>& tiles);
 at::Tensor dequantize_q8(const at::Tensor& in, double scale, double zp);
 void copy_device_to_host_ptr(const at::Tensor& src, void* dst, size_t n,
                              int mode);
@@ -762,10 +763,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("batch"), py::arg("seq"), py::arg("mask"), py::arg("types"),
         py::arg("tok"), py::arg("pos"), py::arg("typ"), py::arg("gamma"),
         py::arg("beta"), py::arg("eps"), py::arg("pad_id"),
-        py::arg("out_dtype"), py::arg("check") = true);
+        py::arg("out_dtype"), py::arg("check") = true,
+        py::arg("packed") = false);
   m.def("masked_self_attention", &mi355x::masked_self_attention,
         py::arg("qkv"), py::arg("lengths"), py::arg("heads"),
-        py::arg("scale"));
+        py::arg("scale"), py::arg("tiles") = py::none());
   m.def("quantize_q8", &mi355x::quantize_q8, py::arg("input"),
         py::arg("scale"), py::arg("zero_point") = 0.0);
   m.def("dequantize_q8", &mi355x::dequantize_q8, py::arg("input"),

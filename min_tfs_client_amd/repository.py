@@ -39,9 +39,11 @@ On-disk version-directory formats understood by the default loader:
                                kernel, or "ids_ragged": unpadded ids plus
                                "sequence_lengths" into the same kernel),
                                "dtype" ("float32", the default, "bfloat16"
-                               or "float16") and "attention" ("sdpa", or
+                               or "float16") and "attention" ("sdpa",
                                "fused": the length-masked MFMA attention
-                               kernel, with "ids_ragged" and a 16-bit
+                               kernel, or "packed": that kernel's packed
+                               form with every layer on the unpadded
+                               rows; both with "ids_ragged" and a 16-bit
                                "dtype");
                                vit_b16
                                takes "input_format" ("float_nchw",

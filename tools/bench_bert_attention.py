@@ -3,6 +3,7 @@
 ``BertLayer`` does by default, one GPU.
 
     python tools/bench_bert_attention.py        # JSON lines
+    python tools/bench_bert_attention.py --packed
 
 The parent process never touches the GPU. Every case runs in a fresh child
 process under its own time limit, and the tool exits non-zero on the first
@@ -21,6 +22,14 @@ Cases: 128 x 512 all full length; 128 x 512 with seeded lengths uniform in
 16..512; 8 x 128 with mixed lengths; 1 x 32. ``needed_tflops`` counts the
 FLOPs the lengths actually ask for, 4 * 64 * heads * sum(L^2) (kept keys x
 kept queries, both matmuls), over the fused kernel's time.
+
+``--packed``: the packed (varlen) form against the padded fused kernel on
+the full, ragged and mixed cases, in the same interleaved rounds: the op
+alone (``qkv [T,3H]`` with ``ops.attention_tiles`` against ``qkv [B,S,3H]``
+with ``lengths``; both table orders, sequence order and longest sequence
+first, each built here from the helper's table), and one full ``BertLayer``
+forward in bf16 (H 768), packed ``[T,H]`` against padded ``[B,S,H]`` with
+``lengths``, which is the figure the packed path exists for.
 """
 import argparse
 import json
@@ -32,6 +41,7 @@ _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, _ROOT)
 
 CASES = ["128x512_full", "128x512_ragged", "8x128_mixed", "1x32_full"]
+PACKED_CASES = CASES[:3]
 STEP_TIMEOUT_S = 240
 HEADS, HEAD_DIM = 12, 64
 
@@ -58,6 +68,87 @@ def rounds_of(fns, reps, rounds=7):
     return [(c[rounds // 2], c[0], c[-1]) for c in cols]
 
 
+def case_lengths(name, g):
+    import torch
+
+    shape, kind = name.split("_")
+    B, S = (int(d) for d in shape.split("x"))
+    if kind == "full":
+        return B, S, torch.full((B,), S)
+    if kind == "ragged":
+        return B, S, torch.randint(16, S + 1, (B,), generator=g)
+    return B, S, torch.tensor([S, S // 2, 7, S - 1, 33, 64, 65, 100][:B])
+
+
+def stats(prefix, t):
+    return {f"{prefix}_ms": round(t[0], 4), f"{prefix}_min_ms": round(t[1], 4),
+            f"{prefix}_max_ms": round(t[2], 4)}
+
+
+def run_packed_case(name):
+    import torch
+
+    from min_tfs_client_amd import ops
+    from min_tfs_client_amd.models.bert import BertConfig, BertLayer
+
+    ops.require_native()
+    dev = "cuda:0"
+    H = HEADS * HEAD_DIM
+    g = torch.Generator().manual_seed(0)
+    B, S, lengths = case_lengths(name, g)
+    T = int(lengths.sum())
+    keep = (torch.arange(S)[None, :] < lengths[:, None]).to(dev)
+    lens = lengths.to(torch.int32).to(dev)
+    qkv = torch.randn(B, S, 3 * H, generator=g).to(torch.bfloat16).to(dev)
+    qkv_p = qkv[keep].contiguous()
+    # both orders from the helper's table, whichever it emits
+    table = ops.attention_tiles(lengths)
+    by_seq = table[torch.argsort(table[:, 3] * (1 << 20) + table[:, 2])]
+    longest = by_seq[torch.argsort(-by_seq[:, 1], stable=True)]
+    by_seq, longest = by_seq.to(dev), longest.to(dev)
+
+    def padded():
+        return ops.masked_self_attention(qkv, lens, HEADS)
+
+    def packed_seq():
+        return ops.masked_self_attention(qkv_p, None, HEADS, tiles=by_seq)
+
+    def packed_longest():
+        return ops.masked_self_attention(qkv_p, None, HEADS, tiles=longest)
+
+    same = bool(torch.equal(padded()[keep], packed_seq())) and \
+        bool(torch.equal(packed_seq(), packed_longest()))
+    # windows of tens of milliseconds: the differences looked for are small
+    reps = 200 if B * S >= 8192 else 2000
+    t_pad, t_seq, t_long = rounds_of((padded, packed_seq, packed_longest),
+                                     reps)
+
+    torch.manual_seed(0)
+    layer = BertLayer(BertConfig()).to(device=dev,
+                                       dtype=torch.bfloat16).eval()
+    x = torch.randn(B, S, H, generator=g).to(torch.bfloat16).to(dev)
+    x_p = x[keep].contiguous()
+    with torch.no_grad():
+        def layer_padded():
+            return layer(x, None, lens)
+
+        def layer_packed():
+            return layer(x_p, None, None, by_seq)
+
+        layer_diff = (layer_padded()[keep].float()
+                      - layer_packed().float()).abs().max().item()
+        l_pad, l_pack = rounds_of((layer_padded, layer_packed),
+                                  40 if B * S >= 8192 else 400)
+    print(json.dumps({
+        "case": name, "mode": "packed", "tokens": T, "padded_tokens": B * S,
+        "token_share": round(T / (B * S), 3), "bit_identical": same,
+        **stats("padded", t_pad), **stats("packed_seq_order", t_seq),
+        **stats("packed_longest_first", t_long),
+        **stats("layer_padded", l_pad), **stats("layer_packed", l_pack),
+        "layer_packed_over_padded": round(l_pack[0] / l_pad[0], 3),
+        "layer_max_abs_diff_kept": layer_diff}), flush=True)
+
+
 def run_case(name):
     import torch
     import torch.nn.functional as F
@@ -67,16 +158,9 @@ def run_case(name):
 
     ops.require_native()
     dev = "cuda:0"
-    shape, kind = name.split("_")
-    B, S = (int(d) for d in shape.split("x"))
     H = HEADS * HEAD_DIM
     g = torch.Generator().manual_seed(0)
-    if kind == "full":
-        lengths = torch.full((B,), S)
-    elif kind == "ragged":
-        lengths = torch.randint(16, S + 1, (B,), generator=g)
-    else:
-        lengths = torch.tensor([S, S // 2, 7, S - 1, 33, 64, 65, 100][:B])
+    B, S, lengths = case_lengths(name, g)
     qkv = torch.randn(B, S, 3 * H, generator=g).to(torch.bfloat16).to(dev)
     lens = lengths.to(torch.int32).to(dev)
     keep = (torch.arange(S)[None, :] < lengths[:, None]).to(dev)
@@ -126,11 +210,13 @@ def run_step(args):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--case", choices=CASES, help="(child) run one case")
+    ap.add_argument("--packed", action="store_true",
+                    help="the packed form against the padded fused kernel")
     a = ap.parse_args()
     if a.case:
-        return run_case(a.case)
-    for name in CASES:
-        run_step(["--case", name])
+        return (run_packed_case if a.packed else run_case)(a.case)
+    for name in PACKED_CASES if a.packed else CASES:
+        run_step(["--case", name] + (["--packed"] if a.packed else []))
 
 
 if __name__ == "__main__":
