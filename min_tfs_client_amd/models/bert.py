@@ -36,7 +36,7 @@ class BertLayer(nn.Module):
         self.heads = cfg.heads
         self.head_dim = h // cfg.heads
 
-    def forward(self, x, attn_mask, lengths=None, tiles=None):
+    def forward(self, x, attn_mask, lengths=None, tiles=None, keys=None):
         """``lengths`` (int32 (B) on x's device): every mask is the prefix
         given by its length, and attention runs in the fused length-masked
         kernel on the projection as stored, with no transposed views, no
@@ -46,11 +46,15 @@ class BertLayer(nn.Module):
         ``tiles`` (``ops.attention_tiles`` on x's device): ``x`` is packed,
         (T,H) with the sequences back to back, and the projection goes to
         the packed form of the same kernel; every other layer of the block
-        is row-wise and runs on the T rows as it is."""
-        if lengths is not None or tiles is not None:
+        is row-wise and runs on the T rows as it is.
+
+        ``keys`` (``ops.attention_keys`` of the request's (B,S) mask, on x's
+        device): an arbitrary key mask in the keys form of the same kernel.
+        Every query row is computed, as the additive mask would have it."""
+        if lengths is not None or tiles is not None or keys is not None:
             from .. import ops
             attn = ops.masked_self_attention(self.qkv(x), lengths, self.heads,
-                                             tiles=tiles)
+                                             tiles=tiles, keys=keys)
             x = self.ln1(x + self.attn_out(attn))
             return self.ln2(
                 x + self.ff2(torch.nn.functional.gelu(self.ff1(x))))
@@ -106,15 +110,16 @@ class BertEncoder(nn.Module):
         return (1.0 - m) * torch.finfo(dtype).min
 
     def forward_embedded(self, x, mask, lengths=None, tiles=None,
-                         first_rows=None):
+                         first_rows=None, keys=None):
         """The encoder blocks and the pooler on an embedded input. With
         ``lengths`` every block runs the fused length-masked attention (see
         ``BertLayer.forward``); all blocks share the one tensor. With
         ``tiles`` the input is packed (T,H) and stays packed through every
         block; ``first_rows`` (int64 (B)) is the first row of each sequence,
-        which the pooler reads."""
+        which the pooler reads. With ``keys`` every block runs the keys
+        form on the one (index, count) pair."""
         for blk in self.blocks:
-            x = blk(x, mask, lengths, tiles)
+            x = blk(x, mask, lengths, tiles, keys)
         first = x[:, 0] if tiles is None else x.index_select(0, first_rows)
         pooled = torch.tanh(self.pooler(first))
         return x, pooled
@@ -198,6 +203,22 @@ def bert_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
     is exactly +0.0 at padded positions; kept positions, "pooled_output"
     and "sentence_embedding" follow the default mode as ``"fused"`` does.
 
+    ``attention="masked"``: the same kernel for the DENSE request, "ids" or
+    "ids_fused" with any "attention_mask": prefixes, left padding, holes.
+    One launch per request (``ops.attention_keys``) turns the mask into the
+    ascending list of kept key positions of every sequence, and every block
+    runs the keys form of ``ops.masked_self_attention`` on that one pair: it
+    loads K and V rows through the list, so key tiles cost what the kept keys
+    cost and masked K and V rows are never read. Every query row is
+    computed, so "last_hidden_state" follows the default mode within
+    bf16 / f16 noise at ALL positions, padded ones included, and so do
+    "pooled_output" and "sentence_embedding"; a sequence with nothing kept
+    gets the default mode's uniform average. It needs a bfloat16 or float16
+    ``dtype`` with 64-wide heads; ``input_format="ids_ragged"`` has no mask
+    and is a ``ValueError`` naming ``"fused"`` / ``"packed"``. A request
+    without "attention_mask" runs the length form with full lengths. The
+    additive mask is not built on this path.
+
     ``output_format="hidden"`` (default): outputs "last_hidden_state"
     (B,S,768) + "pooled_output" (B,768), both DT_FLOAT.
     ``output_format="sentence_embedding"``: the only output is
@@ -218,15 +239,21 @@ def bert_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
         raise ValueError(
             f"input_format must be 'ids', 'ids_fused' or 'ids_ragged', got "
             f"{input_format!r}")
-    if attention not in ("sdpa", "fused", "packed"):
+    if attention not in ("sdpa", "fused", "packed", "masked"):
         raise ValueError(
-            f"attention must be 'sdpa' or 'fused' or 'packed', got "
-            f"{attention!r}")
+            f"attention must be 'sdpa' or 'fused' or 'packed' or 'masked', "
+            f"got {attention!r}")
     cfg = BertConfig() if config is None else config
     fused_attention = attention == "fused"
     packed_attention = attention == "packed"
-    if fused_attention or packed_attention:
-        if input_format != "ids_ragged":
+    masked_attention = attention == "masked"
+    if masked_attention and input_format == "ids_ragged":
+        raise ValueError(
+            "attention='masked' needs input_format='ids' or 'ids_fused' (a "
+            "request with an attention_mask); 'ids_ragged' has lengths: use "
+            "attention='fused' or 'packed'")
+    if attention != "sdpa":
+        if not masked_attention and input_format != "ids_ragged":
             raise ValueError(
                 f"attention={attention!r} needs input_format='ids_ragged' "
                 "(the only mode whose masks are prefixes given by lengths), "
@@ -328,10 +355,32 @@ def bert_servable(device: str = "cpu", dtype=torch.float32, seed: int = 0,
                 pinned_to_device(torch.from_numpy(lens))[:, None]
         return hidden, pooled, mask
 
+    def masked_forward(inputs):
+        """(hidden, pooled, pooling mask) of a dense request whose blocks run
+        the keys form of the attention kernel: the mask goes to the device
+        once, one launch compacts it and all blocks share the pair. The
+        additive mask is not built (the fused embedding still returns one,
+        which is not passed on)."""
+        m = s.module
+        if fused:
+            x, _, mask = fused_embed(inputs)
+        else:
+            mask = on_device(inputs.get("attention_mask"))
+            x = m.embed(on_device(inputs["input_ids"]))
+        if mask is None:
+            # no mask: the length form with every sequence S long
+            B, S = x.shape[:2]
+            lengths = torch.full((B,), S, dtype=torch.int32, device=x.device)
+            return m.forward_embedded(x, None, lengths) + (None,)
+        keys = ops.attention_keys(mask)
+        return m.forward_embedded(x, None, keys=keys) + (mask,)
+
     @torch.no_grad()
     def fn(inputs):
         if packed_attention:
             hidden, pooled, mask = packed_forward(inputs)
+        elif masked_attention:
+            hidden, pooled, mask = masked_forward(inputs)
         elif fused or ragged:
             x, add_mask, mask = fused_embed(inputs)
             lengths = device_lengths(inputs["sequence_lengths"]) \

@@ -1676,7 +1676,43 @@ def attention_tiles(lengths, device=None):
     return table.to(device, non_blocking=True)
 
 
-def masked_self_attention(qkv, lengths, heads, scale=None, *, tiles=None):
+def attention_keys(mask):
+    """The key table of the keys form of :func:`masked_self_attention`:
+    ``(index int32 [B,S], count int32 [B])`` of a ``[B,S]`` keep mask.
+    ``index[b, :count[b]]`` holds the positions ``s`` with ``mask[b,s] != 0``
+    in ascending order; entries at and past ``count[b]`` are unspecified and
+    are never read.
+
+    ``mask`` is an integer or bool tensor, the rules of
+    :func:`masked_mean_pool`: int32, uint8 and bool go to the kernel as they
+    are, other integer dtypes are reduced with ``mask != 0`` first, a float
+    mask is a ``ValueError``. A device mask is compacted by one launch (one
+    wave per sequence, no host synchronization, deterministic); a CPU mask by
+    a stable argsort, with the same result."""
+    name = "attention_keys"
+    if not isinstance(mask, torch.Tensor):
+        raise ValueError(f"{name} expects a torch tensor")
+    if mask.dim() != 2:
+        raise ValueError(f"{name} expects [B,S], got rank {mask.dim()}")
+    if mask.is_floating_point() or mask.is_complex():
+        raise ValueError(
+            f"{name}: mask must be an integer or bool tensor, got "
+            f"{mask.dtype}")
+    if mask.shape[1] >= 1 << 30:
+        raise ValueError(f"{name}: S must be below 2^30")
+    if mask.dtype not in (torch.int32, torch.uint8, torch.bool):
+        mask = mask != 0       # e.g. int64: 1 << 32 is still "keep"
+    mask = mask.contiguous()
+    if mask.is_cuda:
+        return require_native().attention_keys(mask)
+    keep = mask != 0
+    # stable: the kept positions first, each group in ascending order
+    index = torch.argsort(~keep, dim=1, stable=True).to(torch.int32)
+    return index.contiguous(), keep.sum(1, dtype=torch.int32)
+
+
+def masked_self_attention(qkv, lengths, heads, scale=None, *, tiles=None,
+                          keys=None):
     """Fused length-masked multi-head self-attention: the ``[B,S,3*H]`` qkv
     projection (bf16 or f16, contiguous, last axis ordered ``(3, heads,
     head_dim)`` as ``BertLayer.qkv`` emits it, ``head_dim == 64``) ->
@@ -1712,6 +1748,25 @@ def masked_self_attention(qkv, lengths, heads, scale=None, *, tiles=None):
     row0`` and ``q0`` to ``>= 0`` on the device, and an entry with ``q0 >=
     L`` does nothing. Rows of ``out`` that no entry covers are unspecified.
 
+    Keys form, for an arbitrary key mask: ``keys=(index, count)`` (keyword
+    only, from :func:`attention_keys`: int32 ``[B,S]`` and ``[B]``,
+    contiguous, on the device of ``qkv``) with a rank-3 ``qkv`` and neither
+    ``lengths`` nor ``tiles``. With ``c = clamp(count[b], 0, S)`` and every
+    index clamped to ``0..S-1``::
+
+        c > 0:  out[b,s] = softmax_{j<c}((q_s . k_index[b,j]) * scale)
+                           @ v_index[b,j]                     for EVERY s < S
+        c == 0: out[b,s] = mean_{j<S} v_j                     for every s < S
+
+    This is what ``scaled_dot_product_attention`` gives with the additive
+    ``finfo.min`` mask, padded queries and a row with nothing kept (a uniform
+    softmax over all S keys) included. K and V rows of masked positions are
+    never loaded, so a NaN there reaches no output; all Q rows are. The cost
+    follows the number of kept keys, wherever they lie. A query's result
+    depends only on its own row and on the order of the kept keys, so
+    ``out[b, kept]`` equals ``masked_self_attention(qkv[b, kept][None], None,
+    heads, scale)[0]`` bit for bit when ``c > 0``.
+
     Device tensors run the gfx950 MFMA kernel only (no eager fallback, no
     host synchronization: the lengths are clamped on the device); CPU tensors
     run an eager fp32 expression with the same semantics (the packed form:
@@ -1719,8 +1774,10 @@ def masked_self_attention(qkv, lengths, heads, scale=None, *, tiles=None):
     work too. Invalid arguments raise ``ValueError`` on both paths, before
     any launch: among them a rank other than 2 or 3, a rank-2 ``qkv``
     without ``tiles`` or with ``lengths``, ``tiles`` with a rank-3 ``qkv``,
-    ``tiles`` of the wrong dtype, shape or device. ``B == 0``, ``S == 0`` or
-    ``T == 0`` returns an empty tensor."""
+    ``tiles`` of the wrong dtype, shape or device, ``keys`` together with
+    ``lengths`` or ``tiles`` or a rank-2 ``qkv``, either tensor of ``keys``
+    of the wrong dtype, shape, device or contiguity. ``B == 0``, ``S == 0``
+    or ``T == 0`` returns an empty tensor."""
     name = "masked_self_attention"
     if not isinstance(qkv, torch.Tensor):
         raise ValueError(f"{name} expects a torch tensor")
@@ -1756,6 +1813,14 @@ def masked_self_attention(qkv, lengths, heads, scale=None, *, tiles=None):
     scale = float(scale)
     if not math.isfinite(scale):
         raise ValueError(f"{name}: scale must be finite, got {scale}")
+    if keys is not None:
+        if lengths is not None or tiles is not None:
+            raise ValueError(
+                f"{name}: keys exclude lengths and tiles: the key table is "
+                "the mask")
+        if packed:
+            raise ValueError(
+                f"{name}: keys go with a rank-3 qkv, got rank 2")
     if packed:
         if tiles is None:
             raise ValueError(
@@ -1786,6 +1851,27 @@ def masked_self_attention(qkv, lengths, heads, scale=None, *, tiles=None):
     elif tiles is not None:
         raise ValueError(
             f"{name}: tiles go with a rank-2 (packed) qkv, got rank 3")
+    if keys is not None:
+        if not isinstance(keys, (tuple, list)) or len(keys) != 2:
+            raise ValueError(
+                f"{name}: keys must be the (index, count) pair of "
+                "attention_keys")
+        for what, t, shape in (("index", keys[0], (B, S)),
+                               ("count", keys[1], (B,))):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+                raise ValueError(
+                    f"{name}: keys {what} must be an int32 tensor, got "
+                    f"{getattr(t, 'dtype', type(t))}")
+            if tuple(t.shape) != shape:
+                raise ValueError(
+                    f"{name}: keys {what} must have shape {list(shape)}, "
+                    f"got {list(t.shape)}")
+            if t.device != qkv.device:
+                raise ValueError(
+                    f"{name}: keys {what} is on {t.device} but qkv is on "
+                    f"{qkv.device}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name}: keys {what} must be contiguous")
     if lengths is not None:
         if not isinstance(lengths, torch.Tensor) or \
                 lengths.dtype != torch.int32:
@@ -1800,9 +1886,26 @@ def masked_self_attention(qkv, lengths, heads, scale=None, *, tiles=None):
                 f"{qkv.device}")
         lengths = lengths.contiguous()
     if qkv.is_cuda:
+        if keys is not None:
+            return require_native().masked_self_attention(
+                qkv, None, heads, scale, None, keys[0], keys[1])
         return require_native().masked_self_attention(qkv, lengths, heads,
                                                       scale, tiles)
     H = H3 // 3
+    if keys is not None:
+        # the kernel's rule, clamps included: a gather of the kept K and V
+        # rows, so a masked row is never read; nothing kept: the plain mean
+        out = qkv.new_empty((B, S, H))
+        x = qkv.float().view(B, S, 3, heads, head_dim)
+        for b in range(B):
+            c = min(max(int(keys[1][b]), 0), S)
+            kept = keys[0][b, :c].long().clamp(0, S - 1) if c else \
+                torch.arange(S)
+            q, k, v = x[b, :, 0], x[b, kept, 1], x[b, kept, 2]  # [*,heads,64]
+            scores = torch.einsum("shd,jhd->hsj", q, k) * (scale if c else 0.)
+            out[b] = torch.einsum("hsj,jhd->shd", torch.softmax(scores, -1),
+                                  v).reshape(S, H).to(qkv.dtype)
+        return out
     if packed:
         # the kernel's walk over the table, clamps included; uncovered rows
         # are unspecified (zeros here)

@@ -22,7 +22,8 @@
 // 16 rows are all padding takes part in the staging and the barriers and
 // skips the arithmetic.
 //
-// Packed (varlen) form, the template parameter PACKED of the one body. qkv is
+// Packed (varlen) form, a value of the template parameter FORM of the one
+// body. qkv is
 // [T,3*H] and out [T,H], sequences back to back with no padding, and an int32
 // table [ntiles,4] holds one row (row0, L, q0, seq) per 64-row query tile:
 // the sequence's first packed row, its length, the tile's first query (a
@@ -54,6 +55,38 @@
 //    overlap, so longest first is kept and sequence order is not an option.
 //    At full length (274 us) and at 8 x 128 (5.9 us, launch bound) the order
 //    makes no measurable difference.
+//
+// Keys form, the third value of the template parameter FORM: an arbitrary
+// key mask [B,S], as a dense request's attention_mask is. A mask with c kept
+// keys is the prefix case behind one indirection: attention_keys_kernel (one
+// launch per request, one wave per sequence) writes the ascending list of
+// kept positions index[b, :c] and c = count[b], every block of the model
+// shares the pair, and this kernel walks ceil(c/64) key tiles and loads K and
+// V row index[b, j] where the padded form loads row j. Only the last tile is
+// partial, exactly as there, and cost follows the kept keys wherever they
+// lie. The grid is the padded form's.
+//  * Every query row s < S is loaded, computed and stored: a padded query
+//    attends to the kept keys, which is what the additive finfo.min mask of
+//    the library path gives, so the encoder's output matches that path at
+//    padded positions too. K and V rows of masked positions are never
+//    loaded.
+//  * c == 0: under the additive mask every score rounds to finfo.min and the
+//    softmax is uniform over ALL S keys. Here: c = S, identity index (no
+//    table read), score scale 0.
+//  * Clamps: count to 0..S, each index to 0..S-1, on the device: no table
+//    can make the kernel touch a row outside the sequence.
+//  * A query's result depends only on its own row and on the order and
+//    tiling of the keys, so out[b, kept] is bit-identical to the padded form
+//    run on the compacted sequence qkv[b, kept].
+//  * The new cost is a dependent load, index then row. The thread's four
+//    indices of tile t + 2 are fetched right after the row loads of tile
+//    t + 1 are issued, one whole tile of arithmetic before they are used, so
+//    no row load waits on an index load of its own step (only tile 0 does).
+//    That is 4 more VGPRs. The alternative, staging the sequence's whole
+//    list in LDS once, was not built: the 4 KB left under the 40 KB that
+//    keep four workgroups per CU hold 1024 indices, so S > 1024 would need
+//    a second path, and it adds a barrier before the first tile. Neither has
+//    been timed on an MI355X yet; profiles/README.md says what to measure.
 //
 // Small problems. There is one tile. B = 1, S = 128 is 24 workgroups of 2 key
 // tiles on 256 CUs, and such a launch is bound by the launch itself: measured
@@ -122,11 +155,14 @@
 // --cuda-device-only -Rpass-analysis=kernel-resource-usage; the build does
 // not pass the last two):
 //   dtype  form    VGPRs  AGPRs  SGPRs  LDS bytes  scratch  occupancy (waves/SIMD)
-//   bf16   padded    100     16     62      36864        0     4
-//   f16    padded    100     16     62      36864        0     4
-//   bf16   packed     94     16     61      36864        0     4
-//   f16    packed     94     16     61      36864        0     4
-// 4 waves/SIMD is 4 workgroups per CU, 144 KB of its 160 KB of LDS.
+//   bf16   padded     99     16     60      36864        0     4
+//   f16    padded     99     16     60      36864        0     4
+//   bf16   packed     97     16     61      36864        0     4
+//   f16    packed     97     16     61      36864        0     4
+//   bf16   keys      103     16     68      36864        0     4
+//   f16    keys      103     16     68      36864        0     4
+// 4 waves/SIMD is 4 workgroups per CU, 144 KB of its 160 KB of LDS. The
+// key-index kernel (both mask widths): 6 VGPRs, 21 SGPRs, no LDS, 0 scratch.
 #include <hip/hip_runtime.h>
 
 #include <torch/extension.h>
@@ -137,6 +173,7 @@
 #include <limits>
 #include <stdexcept>
 #include <string>
+#include <tuple>
 
 namespace mi355x {
 namespace {
@@ -173,19 +210,27 @@ struct AttnParams {
   const void* qkv;          // [B,S,3H], packed: [T,3H]
   const int32_t* lengths;   // [B] or null (padded form only)
   const int32_t* tiles;     // packed: [ntiles,4] of (row0, L, q0, seq)
+  const int32_t* index;     // keys: [B,S] kept key positions, ascending
+  const int32_t* count;     // keys: [B] number of kept keys
   void* out;                // [B,S,H], packed: [T,H]
   int S, heads, qtiles;     // packed: S is T, qtiles is unused
   float scale_log2e;        // scale * log2(e)
 };
 
-// PACKED selects where a workgroup finds its work, nothing else: the padded
-// form derives (b, head, tile) from blockIdx.x and reads lengths[b]; the
-// packed form reads one row of the tile table. From `q0`, `L`, `S` (the
-// first row index that is not stored) and the two base pointers on, the body
-// is one.
-template <typename T, bool PACKED>
+enum AtForm { kAtPadded, kAtPacked, kAtKeys };
+
+// FORM selects where a workgroup finds its work and which row a key slot
+// names, nothing else: the padded form derives (b, head, tile) from
+// blockIdx.x and reads lengths[b]; the packed form reads one row of the tile
+// table; the keys form has the padded form's grid, reads count[b] and looks
+// key slot j up in index[b, j]. From `q0`, `L` (keys), `QL` (queries that
+// are computed), `S` (the first row index that is not stored) and the two
+// base pointers on, the body is one.
+template <typename T, int FORM>
 __global__ __launch_bounds__(kAtThreads)
 void attention_kernel(const AttnParams p) {
+  constexpr bool PACKED = FORM == kAtPacked;
+  constexpr bool KEYS = FORM == kAtKeys;
   using E = typename T::E;
   using V8 = typename T::V8;
   using V4 = typename T::V4;
@@ -202,6 +247,8 @@ void attention_kernel(const AttnParams p) {
   const int64_t row3 = int64_t(3) * H;          // elements per qkv row
   int head, L, S, q0;
   int64_t first;                                // row of the sequence's s = 0
+  float scale_log2e = p.scale_log2e;
+  const int32_t* index = nullptr;               // keys form: slot -> key row
   if constexpr (PACKED) {
     head = int(wg % uint32_t(p.heads));
     // one 16-byte scalar read; the clamps make any table harmless
@@ -224,13 +271,27 @@ void attention_kernel(const AttnParams p) {
     L = L < 0 ? 0 : (L > S ? S : L);
     q0 = qt * kAtBM;
     first = b * S;
+    if constexpr (KEYS) {
+      L = p.count[b];
+      L = L < 0 ? 0 : (L > S ? S : L);
+      index = p.index + b * S;
+      if (L == 0) {
+        // nothing kept: what the additive finfo.min mask gives, the uniform
+        // softmax over all S keys (every score is 0, the index the identity)
+        L = S;
+        scale_log2e = 0.f;
+        index = nullptr;
+      }
+    }
   }
+  // the keys form computes and stores every query row; the others stop at L
+  const int QL = KEYS ? S : L;
 
   const E* const qkv = static_cast<const E*>(p.qkv) + first * row3 +
                        head * kAtD;
   E* const out = static_cast<E*>(p.out) + first * H + head * kAtD;
 
-  if (!PACKED && q0 >= L) {
+  if (FORM == kAtPadded && q0 >= L) {
     // the whole tile is padding: 64 rows x 128 bytes of zeros, rows < S only
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -247,12 +308,12 @@ void attention_kernel(const AttnParams p) {
   union Frag { uint4 u; V8 f; };
   Frag qf[2];
   qf[0].u = qf[1].u = make_uint4(0u, 0u, 0u, 0u);
-  if (qs < L) {
+  if (qs < QL) {
     const E* src = qkv + int64_t(qs) * row3 + g * 8;
     qf[0].u = *reinterpret_cast<const uint4*>(src);
     qf[1].u = *reinterpret_cast<const uint4*>(src + 32);
   }
-  const bool live = q0 + wave * 16 < L;         // wave-uniform
+  const bool live = q0 + wave * 16 < QL;        // wave-uniform
 
   // staging roles. K: row (tid / 8) + 32 i, 16-byte chunk tid % 8.
   // V: key pair lane % 32 (keys 2kp, 2kp + 1), d chunk 2 * wave + lane / 32.
@@ -262,6 +323,28 @@ void attention_kernel(const AttnParams p) {
   const int v_col = (v_key & 32) + 8 * ((v_key >> 2) & 3) +
                     4 * ((v_key >> 4) & 1) + (v_key & 3);
   uint4 kr[2], vr[2];
+  // rows of the thread's two K and two V slots of one tile. Padded and
+  // packed: the slot itself. Keys: index[slot], clamped to 0..S-1, fetched
+  // one tile ahead of the rows (see "Keys form" in the header); slots at or
+  // past L are not looked up and not loaded.
+  int krow[2], vrow[2];
+  auto fetch = [&](int t) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int kj = t * kAtBN + k_key + 32 * i;
+      const int vj = t * kAtBN + v_key + i;
+      krow[i] = kj;
+      vrow[i] = vj;
+      if constexpr (KEYS) {
+        if (index != nullptr) {                 // workgroup-uniform
+          const int a = kj < L ? index[kj] : 0;
+          const int c = vj < L ? index[vj] : 0;
+          krow[i] = a < 0 ? 0 : (a >= S ? S - 1 : a);
+          vrow[i] = c < 0 ? 0 : (c >= S ? S - 1 : c);
+        }
+      }
+    }
+  };
   auto load = [&](int t) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -269,12 +352,12 @@ void attention_kernel(const AttnParams p) {
       kr[i] = make_uint4(0u, 0u, 0u, 0u);
       if (kj < L)
         kr[i] = *reinterpret_cast<const uint4*>(
-            qkv + int64_t(kj) * row3 + H + k_chunk * 8);
+            qkv + int64_t(krow[i]) * row3 + H + k_chunk * 8);
       const int vj = t * kAtBN + v_key + i;
       vr[i] = make_uint4(0u, 0u, 0u, 0u);
       if (vj < L)
         vr[i] = *reinterpret_cast<const uint4*>(
-            qkv + int64_t(vj) * row3 + 2 * H + v_chunk * 8);
+            qkv + int64_t(vrow[i]) * row3 + 2 * H + v_chunk * 8);
     }
   };
   auto store = [&](char* buf) {
@@ -302,12 +385,17 @@ void attention_kernel(const AttnParams p) {
   float l = 0.f;
 
   const int ntiles = (L + kAtBN - 1) / kAtBN;
+  fetch(0);
   load(0);
+  fetch(1);
   for (int t = 0; t < ntiles; ++t) {
     char* const buf = smem + (t & 1) * kAtBufBytes;
     store(buf);
     __syncthreads();
-    if (t + 1 < ntiles) load(t + 1);
+    if (t + 1 < ntiles) {
+      load(t + 1);      // its rows were looked up a whole tile ago
+      fetch(t + 2);
+    }
     if (!live) continue;
 
     // S^T: lane (r, g) gets query r against keys k0 + 16 kb + 4g + i
@@ -329,7 +417,7 @@ void attention_kernel(const AttnParams p) {
     for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        float x = s[kb][i] * p.scale_log2e;
+        float x = s[kb][i] * scale_log2e;
         if (partial && k0 + kb * 16 + g * 4 + i >= L)
           x = -std::numeric_limits<float>::infinity();
         s[kb][i] = x;
@@ -386,14 +474,78 @@ void attention_kernel(const AttnParams p) {
       V4 y;
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        y[i] = qs < L ? static_cast<E>(__fdiv_rn(o[db][i], l))
-                      : static_cast<E>(0.f);
+        y[i] = qs < QL ? static_cast<E>(__fdiv_rn(o[db][i], l))
+                       : static_cast<E>(0.f);
       *reinterpret_cast<V4*>(dst + db * 16) = y;
     }
   }
 }
 
+// Key-index kernel of the keys form: one wave per sequence compacts the kept
+// positions of mask[b, :] (non-zero keeps) into index[b, :count[b]],
+// ascending. 64 positions per step: the ballot of the step's keep bits, the
+// popcount of the lower lanes gives a kept lane its slot after the running
+// base, which is wave-uniform and stays in an SGPR. Slots at and past
+// count[b] are not written. Every slot is written by one lane: deterministic.
+template <typename M>
+__global__ __launch_bounds__(64)
+void attention_keys_kernel(const M* __restrict__ mask,
+                           int32_t* __restrict__ index,
+                           int32_t* __restrict__ count, int S) {
+  const int lane = int(threadIdx.x);
+  const int64_t row = int64_t(blockIdx.x) * S;
+  const M* const m = mask + row;
+  int32_t* const dst = index + row;
+  int base = 0;
+  for (int s0 = 0; s0 < S; s0 += 64) {
+    const int s = s0 + lane;
+    const bool keep = s < S && m[s] != M(0);
+    const uint64_t bits = __ballot(keep);
+    const int below = int(__builtin_amdgcn_mbcnt_hi(
+        uint32_t(bits >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(bits), 0u)));
+    if (keep) dst[base + below] = s;
+    base += __popcll(bits);
+  }
+  if (lane == 0) count[blockIdx.x] = base;
+}
+
 }  // namespace
+
+// The key table of the keys form, see attention_keys_kernel: `mask` is a
+// contiguous device [B,S] of int32, uint8 or bool; returns (index int32
+// [B,S], count int32 [B]). One launch, no host synchronization.
+std::tuple<at::Tensor, at::Tensor> attention_keys(const at::Tensor& mask) {
+  const char* who = "attention_keys";
+  const at::ScalarType md = mask.scalar_type();
+  TORCH_CHECK_VALUE(mask.is_cuda() && mask.dim() == 2 && mask.is_contiguous(),
+                    who, " expects a contiguous device [B,S] mask");
+  TORCH_CHECK_VALUE(md == at::kInt || md == at::kByte || md == at::kBool, who,
+                    ": mask must be int32, uint8 or bool, got ", md);
+  const int64_t B = mask.size(0), S = mask.size(1);
+  TORCH_CHECK_VALUE(S < (int64_t(1) << 30) && B < (int64_t(1) << 31), who,
+                    ": S must be below 2^30 and B below 2^31, got B=", B,
+                    " S=", S);
+  auto index = at::empty({B, S}, mask.options().dtype(at::kInt));
+  auto count = at::empty({B}, mask.options().dtype(at::kInt));
+  if (B == 0) return {index, count};            // zero grid: never launch
+  const dim3 grid{uint32_t(B)}, block(64);
+  hipStream_t stream = at::hip::getCurrentHIPStream().stream();
+  int32_t* const ip = static_cast<int32_t*>(index.mutable_data_ptr());
+  int32_t* const cp = static_cast<int32_t*>(count.mutable_data_ptr());
+  if (md == at::kInt)
+    hipLaunchKernelGGL(attention_keys_kernel<int32_t>, grid, block, 0, stream,
+                       static_cast<const int32_t*>(mask.const_data_ptr()), ip,
+                       cp, int(S));
+  else
+    hipLaunchKernelGGL(attention_keys_kernel<uint8_t>, grid, block, 0, stream,
+                       static_cast<const uint8_t*>(mask.const_data_ptr()), ip,
+                       cp, int(S));
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess)
+    throw std::runtime_error(std::string("HIP error: ") +
+                             hipGetErrorString(err) + " at " + who);
+  return {index, count};
+}
 
 // Length-masked self-attention, see the header of this file. Padded form:
 // `qkv` is [B,S,3*heads*64] bf16 or f16, `lengths` int32 [B] on its device or
@@ -402,12 +554,17 @@ void attention_kernel(const AttnParams p) {
 // form: `qkv` is [T,3*heads*64], `tiles` the int32 [n,4] device table of
 // (row0, L, q0, seq) rows and `lengths` is absent; returns [T,heads*64],
 // whose rows outside every entry are unspecified. The entries are clamped on
-// the device and never read back. Arguments the kernel cannot serve are
-// ValueError.
+// the device and never read back. Keys form: `qkv` is [B,S,3*H], `index`
+// int32 [B,S] and `count` int32 [B] come from attention_keys, `lengths` and
+// `tiles` are absent; every row of the [B,S,H] result is computed. Counts
+// and indices are clamped on the device and never read back. Arguments the
+// kernel cannot serve are ValueError.
 at::Tensor masked_self_attention(const at::Tensor& qkv,
                                  const c10::optional<at::Tensor>& lengths,
                                  int64_t heads, double scale,
-                                 const c10::optional<at::Tensor>& tiles) {
+                                 const c10::optional<at::Tensor>& tiles,
+                                 const c10::optional<at::Tensor>& index,
+                                 const c10::optional<at::Tensor>& count) {
   const char* who = "masked_self_attention";
   const at::ScalarType dt = qkv.scalar_type();
   TORCH_CHECK_VALUE(dt == at::kBFloat16 || dt == at::kHalf, who,
@@ -439,6 +596,20 @@ at::Tensor masked_self_attention(const at::Tensor& qkv,
                       lengths->is_contiguous(), who,
                       ": lengths must be a contiguous int32 [", B,
                       "] on qkv's device");
+  const bool keys = index.has_value();
+  TORCH_CHECK_VALUE(keys == count.has_value() &&
+                    !(keys && (packed || lengths.has_value())), who,
+                    ": index and count go together, with a [B,S,3*H] qkv and "
+                    "no lengths");
+  if (keys)
+    for (const at::Tensor* t : {&*index, &*count})
+      TORCH_CHECK_VALUE(t->is_cuda() &&
+                        t->get_device() == qkv.get_device() &&
+                        t->scalar_type() == at::kInt && t->is_contiguous() &&
+                        t->dim() == (t == &*index ? 2 : 1) &&
+                        t->size(0) == B && (t != &*index || t->size(1) == S),
+                        who, ": keys must be contiguous int32 [", B, ",", S,
+                        "] and [", B, "] on qkv's device");
   int64_t ntiles = 0;
   if (packed) {
     TORCH_CHECK_VALUE(tiles->is_cuda() &&
@@ -484,6 +655,10 @@ at::Tensor masked_self_attention(const at::Tensor& qkv,
                   : nullptr;
   p.tiles = packed ? static_cast<const int32_t*>(tiles->const_data_ptr())
                    : nullptr;
+  p.index = keys ? static_cast<const int32_t*>(index->const_data_ptr())
+                 : nullptr;
+  p.count = keys ? static_cast<const int32_t*>(count->const_data_ptr())
+                 : nullptr;
   p.out = out.mutable_data_ptr();
   p.S = int(S);
   p.heads = int(heads);
@@ -492,18 +667,20 @@ at::Tensor masked_self_attention(const at::Tensor& qkv,
 
   const dim3 grid{uint32_t(groups)}, block(kAtThreads);
   hipStream_t stream = at::hip::getCurrentHIPStream().stream();
-  if (dt == at::kBFloat16 && packed)
-    hipLaunchKernelGGL((attention_kernel<AtBf16, true>), grid, block, 0,
-                       stream, p);
-  else if (dt == at::kBFloat16)
-    hipLaunchKernelGGL((attention_kernel<AtBf16, false>), grid, block, 0,
-                       stream, p);
-  else if (packed)
-    hipLaunchKernelGGL((attention_kernel<AtF16, true>), grid, block, 0,
-                       stream, p);
-  else
-    hipLaunchKernelGGL((attention_kernel<AtF16, false>), grid, block, 0,
-                       stream, p);
+  auto launch = [&](auto tag) {
+    using T = decltype(tag);
+    if (packed)
+      hipLaunchKernelGGL((attention_kernel<T, kAtPacked>), grid, block, 0,
+                         stream, p);
+    else if (keys)
+      hipLaunchKernelGGL((attention_kernel<T, kAtKeys>), grid, block, 0,
+                         stream, p);
+    else
+      hipLaunchKernelGGL((attention_kernel<T, kAtPadded>), grid, block, 0,
+                         stream, p);
+  };
+  if (dt == at::kBFloat16) launch(AtBf16{});
+  else launch(AtF16{});
   hipError_t err = hipGetLastError();
   if (err != hipSuccess)
     throw std::runtime_error(std::string("HIP error: ") +

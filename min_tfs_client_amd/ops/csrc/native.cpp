@@ -105,7 +105,10 @@ std::tuple<at::Tensor, c10::optional<at::Tensor>, int64_t> bert_embed(
 at::Tensor masked_self_attention(const at::Tensor& qkv,
                                  const c10::optional<at::Tensor>& lengths,
                                  int64_t heads, double scale,
-                                 const c10::optional<at::Tensor>& tiles);
+                                 const c10::optional<at::Tensor>& tiles,
+                                 const c10::optional<at::Tensor>& index,
+                                 const c10::optional<at::Tensor>& count);
+std::tuple<at::Tensor, at::Tensor> attention_keys(const at::Tensor& mask);
 at::Tensor dequantize_q8(const at::Tensor& in, double scale, double zp);
 void copy_device_to_host_ptr(const at::Tensor& src, void* dst, size_t n,
                              int mode);
@@ -767,7 +770,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("packed") = false);
   m.def("masked_self_attention", &mi355x::masked_self_attention,
         py::arg("qkv"), py::arg("lengths"), py::arg("heads"),
-        py::arg("scale"), py::arg("tiles") = py::none());
+        py::arg("scale"), py::arg("tiles") = py::none(),
+        py::arg("index") = py::none(), py::arg("count") = py::none());
+  m.def("attention_keys", &mi355x::attention_keys, py::arg("mask"));
   m.def("quantize_q8", &mi355x::quantize_q8, py::arg("input"),
         py::arg("scale"), py::arg("zero_point") = 0.0);
   m.def("dequantize_q8", &mi355x::dequantize_q8, py::arg("input"),

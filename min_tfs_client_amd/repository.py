@@ -44,7 +44,9 @@ On-disk version-directory formats understood by the default loader:
                                kernel, or "packed": that kernel's packed
                                form with every layer on the unpadded
                                rows; both with "ids_ragged" and a 16-bit
-                               "dtype");
+                               "dtype"; or "masked": that kernel's keys
+                               form for any "attention_mask", with "ids"
+                               or "ids_fused" and a 16-bit "dtype");
                                vit_b16
                                takes "input_format" ("float_nchw",
                                "uint8_nhwc": raw pixels into the fused

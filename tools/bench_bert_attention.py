@@ -4,6 +4,7 @@
 
     python tools/bench_bert_attention.py        # JSON lines
     python tools/bench_bert_attention.py --packed
+    python tools/bench_bert_attention.py --masked
 
 The parent process never touches the GPU. Every case runs in a fresh child
 process under its own time limit, and the tool exits non-zero on the first
@@ -30,6 +31,15 @@ with ``lengths``; both table orders, sequence order and longest sequence
 first, each built here from the helper's table), and one full ``BertLayer``
 forward in bf16 (H 768), packed ``[T,H]`` against padded ``[B,S,H]`` with
 ``lengths``, which is the figure the packed path exists for.
+
+``--masked``: the keys form (``keys=ops.attention_keys(mask)``, arbitrary
+key masks, every query row computed) on the ragged case, 128 sequences of
+16..512 kept tokens at S = 512, in three mask layouts (the kept tokens as a
+prefix, as a suffix, scattered), in the same interleaved rounds against the
+default layer's chain with the additive mask (what a dense request runs
+without it), against the length form at the same counts (prefix layout only;
+it computes only the kept query rows, so it is the floor) and the
+``ops.attention_keys`` launch alone.
 """
 import argparse
 import json
@@ -42,6 +52,7 @@ sys.path.insert(0, _ROOT)
 
 CASES = ["128x512_full", "128x512_ragged", "8x128_mixed", "1x32_full"]
 PACKED_CASES = CASES[:3]
+MASK_LAYOUTS = ["prefix", "suffix", "scattered"]
 STEP_TIMEOUT_S = 240
 HEADS, HEAD_DIM = 12, 64
 
@@ -149,6 +160,65 @@ def run_packed_case(name):
         "layer_max_abs_diff_kept": layer_diff}), flush=True)
 
 
+def run_masked_case(layout):
+    import torch
+    import torch.nn.functional as F
+
+    from min_tfs_client_amd import ops
+    from min_tfs_client_amd.models.bert import BertEncoder
+
+    ops.require_native()
+    dev = "cuda:0"
+    H = HEADS * HEAD_DIM
+    g = torch.Generator().manual_seed(0)
+    B, S, counts = case_lengths("128x512_ragged", g)
+    prefix = torch.arange(S)[None, :] < counts[:, None]
+    if layout == "prefix":
+        keep = prefix
+    elif layout == "suffix":
+        keep = prefix.flip(1)
+    else:       # each row's kept positions: a seeded random subset
+        rank = torch.rand(B, S, generator=g).argsort(1).argsort(1)
+        keep = rank < counts[:, None]
+    qkv = torch.randn(B, S, 3 * H, generator=g).to(torch.bfloat16).to(dev)
+    mask = keep.to(torch.int32).to(dev)
+    lens = counts.to(torch.int32).to(dev)
+    add_mask = BertEncoder.additive_mask(mask, torch.bfloat16)
+    keys = ops.attention_keys(mask)
+
+    def masked():
+        return ops.masked_self_attention(qkv, None, HEADS, keys=keys)
+
+    def sdpa():
+        q, k, v = (t.transpose(1, 2) for t in
+                   qkv.view(B, S, 3, HEADS, HEAD_DIM).unbind(2))
+        attn = F.scaled_dot_product_attention(q, k, v, attn_mask=add_mask)
+        return attn.transpose(1, 2).reshape(B, S, H)
+
+    def length_form():
+        return ops.masked_self_attention(qkv, lens, HEADS)
+
+    def key_index():
+        return ops.attention_keys(mask)
+
+    diff = (masked().float() - sdpa().float()).abs().max().item()
+    same = None
+    if layout == "prefix":
+        kept = keep.to(dev)
+        same = bool(torch.equal(masked()[kept], length_form()[kept]))
+    t_m, t_s, t_l = rounds_of((masked, sdpa, length_form), 20)
+    t_k, = rounds_of((key_index,), 2000)
+    print(json.dumps({
+        "case": "128x512_ragged", "mode": "masked", "layout": layout,
+        "kept_tokens": int(counts.sum()), "padded_tokens": B * S,
+        **stats("masked", t_m), **stats("sdpa", t_s),
+        **stats("length_form", t_l), **stats("attention_keys", t_k),
+        "sdpa_over_masked": round(t_s[0] / t_m[0], 2),
+        "masked_over_length_form": round(t_m[0] / t_l[0], 2),
+        "prefix_kept_rows_bit_identical": same,
+        "max_abs_diff_all_rows": diff}), flush=True)
+
+
 def run_case(name):
     import torch
     import torch.nn.functional as F
@@ -212,7 +282,18 @@ def main():
     ap.add_argument("--case", choices=CASES, help="(child) run one case")
     ap.add_argument("--packed", action="store_true",
                     help="the packed form against the padded fused kernel")
+    ap.add_argument("--masked", action="store_true",
+                    help="the keys form (arbitrary key masks) against sdpa "
+                         "and the length form")
+    ap.add_argument("--layout", choices=MASK_LAYOUTS,
+                    help="(child, with --masked) run one mask layout")
     a = ap.parse_args()
+    if a.layout:
+        return run_masked_case(a.layout)
+    if a.masked:
+        for layout in MASK_LAYOUTS:
+            run_step(["--masked", "--layout", layout])
+        return
     if a.case:
         return (run_packed_case if a.packed else run_case)(a.case)
     for name in PACKED_CASES if a.packed else CASES:
